@@ -2,7 +2,7 @@
 """Headline benchmark: paired 256x256 stain tiles/s for one full optimisation step of the
 flow-matching U-Net (sample -> forward -> loss -> backward -> gradient all-reduce -> Adam).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -264,10 +264,12 @@ def multitask_flops(tile: int) -> float:
     return 3.0 * (2 * enc + 2 * dec + heads)
 
 
-def multitask_bench(args, dev, rank: int, world: int, use_dist: bool, tile: int, batch: int, steps: int, warmup: int) -> dict:
+def multitask_bench(args, dev, rank: int, world: int, use_dist: bool, tile: int, batch: int, steps: int, warmup: int,
+                    dump: str = None) -> dict:
     """BASELINE.json configs[4] (row f2): the multitask step -- shared encoder on xt and on the source, flow head, mask
     head, Dice + BCE, one Adam over encoder + flow_decoder + seg_decoder (conditional_flow_matching_multitask.py:204-257,
-    391-417) -- as the fused ``MultiTaskTrainer``; 512 x 512 tiles, batch 8 per GPU.  Same timing contract as the headline."""
+    391-417) -- as the fused ``MultiTaskTrainer``; 512 x 512 tiles, batch 8 per GPU.  Same timing contract as the headline.
+    ``dump``: the --dump-outputs directory (the last timed step's outputs)."""
     from stain2stain_amd import FlowMatchingDecoder, MultiTaskTrainer, SegmentationDecoder, SharedEncoder, ops
     torch.manual_seed(1984)
     enc = SharedEncoder(3, FEATURES, precision=args.precision).to(dev).train()
@@ -304,6 +306,8 @@ def multitask_bench(args, dev, rank: int, world: int, use_dist: bool, tile: int,
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     pause.resume()
+    if dump and rank == 0:
+        _dump_outputs(dump, _step_outputs(loss, [enc, fdec, sdec]))
     if use_dist:
         el = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -406,11 +410,56 @@ class _GcPause:
             gc.enable()
 
 
-def pix2pix_bench(args, dev, rank: int, world: int, use_dist: bool) -> dict:
+DUMP_SAMPLE = 1 << 20        # --dump-outputs: elements drawn from a large flat array (4 MB in float32)
+DUMP_LIMIT = 64 << 20        # --dump-outputs: bytes written in all
+
+
+def _sample(x: torch.Tensor, k: int = DUMP_SAMPLE) -> torch.Tensor:
+    """``x`` itself if it has at most ``k`` elements, else ``k`` of its elements at fixed, seeded positions (the same
+    positions in every run of the same configuration), in storage order."""
+    import numpy as np
+    n = x.numel()
+    if n <= k:
+        return x
+    idx = np.sort(np.random.default_rng(1984).choice(n, k, replace=False))
+    return x.reshape(-1)[torch.from_numpy(idx).to(x.device)]
+
+
+def _step_outputs(loss, modules) -> dict:
+    """What a caller of a training step holds after its last call: the loss (or losses) it returned and the modules it
+    updated in place -- a seeded sample of their parameters and of that step's gradients, and their floating-point
+    buffers (BatchNorm running statistics).  Host float32 arrays."""
+    params = [p for m in modules for p in m.parameters()]
+    out = {"loss": torch.as_tensor(loss).detach().float().reshape(-1),
+           "params_sample": _sample(torch.cat([p.detach().float().reshape(-1) for p in params]))}
+    if all(p.grad is not None for p in params):         # (the fused trainers keep every gradient as a view of a flat buffer)
+        out["grads_sample"] = _sample(torch.cat([p.grad.detach().float().reshape(-1) for p in params]))
+    bufs = [b.detach().float().reshape(-1) for m in modules for b in m.buffers() if b.is_floating_point()]
+    if bufs:
+        out["buffers"] = torch.cat(bufs)
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def _dump_outputs(dirname: str, arrays: dict) -> None:
+    """--dump-outputs: DIR/<name>.npy per array, float32 or float64, at most DUMP_LIMIT bytes in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise RuntimeError(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print(f"bench: wrote {', '.join(sorted(arrays))} ({total / 2 ** 20:.1f} MB) to {dirname}", file=sys.stderr)
+
+
+def pix2pix_bench(args, dev, rank: int, world: int, use_dist: bool, dump: str = None) -> dict:
     """BASELINE.json configs[1] as literally worded: 8-level U-Net generator + 70x70 PatchGAN discriminator, batch 16 per
     GPU, bf16, GAN(BCE) + 100 L1, two Adam(2e-4, 0.5/0.999) -- the fused HIP engine (stain2stain_amd.Pix2PixTrainer),
     no torch compute in the step.  Row a13: not in the reference, parity against the torch-layer oracle only.
-    Same timing contract as the main line: barrier + synchronize on both sides, max over ranks."""
+    Same timing contract as the main line: barrier + synchronize on both sides, max over ranks.  ``dump``: the
+    --dump-outputs directory (the last timed step's outputs)."""
     from stain2stain_amd import PatchGANDiscriminator, Pix2PixGenerator, Pix2PixTrainer, ops
     torch.manual_seed(1984)
     G, D = Pix2PixGenerator().to(dev), PatchGANDiscriminator().to(dev)
@@ -451,6 +500,8 @@ def pix2pix_bench(args, dev, rank: int, world: int, use_dist: bool) -> dict:
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     gc_pause.resume()
+    if dump and rank == 0:                       # before the other launch mode's leg steps the same trainer further
+        _dump_outputs(dump, _step_outputs(losses, [G, D]))
     if use_dist:
         el = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -553,7 +604,14 @@ def main() -> None:
     ap.add_argument("--h2d", action="store_true",
                     help="PCIe-inclusive variant for DESIGN.md: every step copies a fresh uint8 batch from pinned host "
                          "memory and runs the GPU crop/flip/normalise kernel before the optimisation step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed loop of the selected mode, write what its last step computed as DIR/<name>.npy "
+                         "(float32, <= 64 MB): training modes loss.npy, params_sample.npy and grads_sample.npy (the "
+                         "updated parameters and that step's gradients, 2^20 elements at seeded positions), buffers.npy "
+                         "(BatchNorm running statistics); --mode sample: sample.npy, the generated batch (rank 0 only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1 (the number of timed steps)")
     globals()["TILE"] = args.tile
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -584,14 +642,14 @@ def main() -> None:
         # BASELINE.json configs[4] defaults: 512 x 512 tiles, batch 8 per GPU (--tile / --batch override them)
         tile = args.tile if args.tile != 256 else 512
         batch = args.batch if args.batch != BATCH_PER_GPU else 8
-        res = multitask_bench(args, dev, rank, world, use_dist, tile, batch, args.steps, args.warmup)
+        res = multitask_bench(args, dev, rank, world, use_dist, tile, batch, args.steps, args.warmup, dump=args.dump_outputs)
         if rank == 0:
             _emit(json.dumps(res))
         if use_dist:
             dist.destroy_process_group()
         return
     if args.mode == "pix2pix":
-        res = pix2pix_bench(args, dev, rank, world, use_dist)
+        res = pix2pix_bench(args, dev, rank, world, use_dist, dump=args.dump_outputs)
         if rank == 0:
             _emit(json.dumps(res))
         if use_dist:
@@ -629,6 +687,8 @@ def main() -> None:
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         gc_pause.resume()
+        if args.dump_outputs and rank == 0:
+            _dump_outputs(args.dump_outputs, {"sample": _sample(out.float(), 8 << 20).cpu().numpy()})
         if use_dist:
             el = torch.tensor([elapsed], device=dev, dtype=torch.float64)
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -737,6 +797,8 @@ def main() -> None:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:          # before the other launch mode's leg steps the same trainer further
+        _dump_outputs(args.dump_outputs, _step_outputs(loss, [net]))
     other_ms = None
     if graph_ok and world == 1 and not args.no_extras:      # (world size 1 only: see pix2pix_bench)
         other_ms = _other_leg(trainer, lambda i: trainer.step(*pool[i % 4], ts[i % len(ts)]), args.steps, use_dist)

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -63,6 +64,27 @@ def test_dropin_path_is_within_ten_percent_of_the_fused_trainer():
     assert abs(dr["vs_fused_trainer"] - dr["ms_per_step"] / d["ms_per_step"]) < 1e-3
     assert dr["vs_fused_trainer"] <= 1.10, dr
     assert 0 < dr["fused_adam"]["final_loss"] < 2 and 0 < dr["torch_adam"]["final_loss"] < 2
+
+
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: what the headline step computed in its last timed step, as float32 .npy files of at most
+    64 MB in all; the loss is the one the line reports, and a second run with the same arguments (seeded inputs, no
+    atomics in the step) writes the same arrays bit for bit."""
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        d = _run("--no-pix2pix", "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(out), steps=3)
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        arrays = {f[:-len(".npy")]: np.load(out / f, allow_pickle=False) for f in sorted(os.listdir(out))}
+        assert set(arrays) == {"loss", "params_sample", "grads_sample", "buffers"}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["params_sample"].shape == arrays["grads_sample"].shape == (1 << 20,)
+        for name, a in arrays.items():
+            assert a.dtype == np.float32 and np.isfinite(a).all(), name
+        assert float(arrays["loss"][0]) == float.fromhex(d["config"]["loss_bits"])
+        runs.append(arrays)
+    for name in runs[0]:
+        np.testing.assert_array_equal(runs[1][name], runs[0][name], err_msg=name)
 
 
 def test_sampling_line():

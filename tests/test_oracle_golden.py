@@ -20,13 +20,25 @@ def _grad_ok(got, ref, scale):
 
 
 @pytest.mark.parametrize("name", ["tiny", "odd3"])
-def test_train_steps_match_reference(name, golden_tiny, golden_odd3):
+def test_train_steps_match_reference(name, golden_tiny, golden_odd3, monkeypatch):
     G = golden_tiny if name == "tiny" else golden_odd3
-    P = sub(G, "init/")
+    # The oracle runs this trajectory in float64.  The stored one is the reference's fp32 run, kept only on a data seed
+    # where it agrees with the reference's fp64 run to 2e-4 at every step (make_golden.py).  An fp32 oracle reproduces it
+    # only to the rounding of the host that wrote it: the conv biases in front of a train-mode BatchNorm have pure-noise
+    # gradients, Adam turns that noise into ~lr-sized steps, and at step 1 the differences flip ReLU decisions (step-1
+    # gradients 4e-3 off with one host thread).  In float64 the result does not depend on the host's thread count or
+    # vector width.  The time embedding is computed in fp32 and cast, as in make_golden.py's fp64 run.
+    time_embedding = O.time_embedding
+    monkeypatch.setattr(O, "time_embedding", lambda t, dim: time_embedding(t, dim).double())
+
+    def f64(x):
+        return x.double() if x.is_floating_point() else x
+
+    P = {k: f64(v) for k, v in sub(G, "init/").items()}
     steps = 0
     while f"step{steps}/x0" in G:
         steps += 1
-    batches = [(G[f"step{s}/x0"], G[f"step{s}/x1"], G[f"step{s}/t"]) for s in range(steps)]
+    batches = [(f64(G[f"step{s}/x0"]), f64(G[f"step{s}/x1"]), f64(G[f"step{s}/t"])) for s in range(steps)]
     # the full multi-step run (Adam moments carried across steps): EVERY step's velocity, loss and gradients against the
     # reference's -- step 1 runs on the oracle's own post-Adam parameters, so its comparison also covers the update
     P_fin, hist = O.train_steps(P, batches, lr=1e-4, weight_decay=1e-5)
