@@ -84,22 +84,11 @@ def _fresh_grads(named: Sequence[Tuple[str, torch.Tensor]]) -> Dict[str, torch.T
     return {n: torch.empty_like(p, dtype=torch.float32) for n, p in named}
 
 
-class _side_wgrads:
+def _side_wgrads(device):
     """Inside a module's autograd backward: the conv weight gradients go to a second HIP stream (engine.run_on_side), where
     they run beside the bandwidth-bound BatchNorm / up-sampling backward passes as in the fused trainer, and the compute
     stream joins it before the gradients are handed back to autograd."""
-
-    def __init__(self, device):
-        self.side = ops.shared_side_stream(device)
-
-    def __enter__(self):
-        self.prev, engine.side_stream = engine.side_stream, self.side
-        return self
-
-    def __exit__(self, *exc):
-        engine.side_stream = self.prev
-        engine.join_side(self.side)
-        return False
+    return engine.side_scope(ops.shared_side_stream(device))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -21,6 +21,7 @@ from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import contextlib
+import threading
 
 import torch
 import torch.distributed as dist
@@ -169,6 +170,37 @@ class ConvBN:
         self._pack_key[dtype] = (w.data_ptr(), w._version, w.device)
 
 
+def _pack_table(cbs: Sequence[ConvBN], dtype: torch.dtype) -> Tuple[torch.Tensor, int]:
+    """The descriptor table of one ops.pack_conv3x3_batched launch over ``cbs`` (their packed buffers allocated once) and
+    its total block count."""
+    rows, start = [], 0
+    for cb in cbs:
+        wf, wd = cb.ensure_buffers(dtype)
+        rows.append([cb.conv.weight.data_ptr(), wf.data_ptr(), wd.data_ptr(), cb.cout, cb.cin, start])
+        start += ((cb.cout + 31) // 32) * ((cb.cin + 31) // 32)
+    return torch.tensor(rows, dtype=torch.int64, device=cbs[0].conv.weight.device), start
+
+
+class Conv3x3Packer:
+    """The fused trainers' repack: ONE launch re-packs the MFMA operands of every 3x3 conv of ``blocks`` ((conv1, conv2)
+    pairs, the encoder's levels first: ``blocks[0][0]`` is the stem) from their master weights, which the fused Adam
+    changes behind torch's version counter."""
+
+    def __init__(self, blocks: Sequence[Tuple[ConvBN, ConvBN]], dtype: torch.dtype):
+        stem = blocks[0][0]
+        # in fp32 mode all but the stem, which reads the master directly (the bf16 stem runs as a packed conv too)
+        self.convs = [cb for pair in blocks for cb in pair
+                      if cb is not stem or (dtype == torch.bfloat16 and cb.cin <= 8)]
+        self.dtype = dtype
+        self.desc, self.total = _pack_table(self.convs, dtype)
+        self.repack()
+
+    def repack(self) -> None:
+        ops.pack_conv3x3_batched(self.desc, self.total, self.dtype)
+        for cb in self.convs:
+            cb.mark_packed(self.dtype)
+
+
 _REPACK_DESC: Dict[tuple, Tuple[torch.Tensor, int]] = {}
 
 
@@ -191,13 +223,9 @@ def repack_stale(cbs: Sequence[ConvBN], dtype: torch.dtype) -> None:
                            for cb, b in zip(stale, bufs))
     hit = _REPACK_DESC.get(key)
     if hit is None:
-        rows, start = [], 0
-        for cb, (wf, wd) in zip(stale, bufs):
-            rows.append([cb.conv.weight.data_ptr(), wf.data_ptr(), wd.data_ptr(), cb.cout, cb.cin, start])
-            start += ((cb.cout + 31) // 32) * ((cb.cin + 31) // 32)
         if len(_REPACK_DESC) > 64:
             _REPACK_DESC.clear()
-        hit = _REPACK_DESC[key] = (torch.tensor(rows, dtype=torch.int64, device=stale[0].conv.weight.device), start)
+        hit = _REPACK_DESC[key] = _pack_table(stale, dtype)
     ops.pack_conv3x3_batched(hit[0], hit[1], dtype)
     for cb in stale:
         cb.mark_packed(dtype)
@@ -309,19 +337,45 @@ def _conv_bn_relu(cb: ConvBN, x0, x1, dtype, training: bool, want_pool: bool = F
 # a leaf: nothing downstream of it but the gradient exchange and Adam.  It is MFMA-bound, while the BatchNorm /
 # up-sampling / pooling backward passes that follow on the critical path are HBM-bound, so the fused trainer issues the
 # weight-gradient launches on a second stream (fork on an event after the layer's BN backward, join before the gradient
-# bucket is exchanged / before Adam) and the two kinds of work share the chip.  ``side_stream`` is None on the
-# autograd-module path (everything on the current stream).
-side_stream: Optional[torch.cuda.Stream] = None
+# bucket is exchanged / before Adam) and the two kinds of work share the chip.  A trainer opens a ``side_scope`` around
+# its backward pass; outside any scope (the autograd-module path without one) everything runs on the current stream.
+class _SideState(threading.local):
+    stream: Optional[torch.cuda.Stream] = None      # the innermost scope's side stream (None: the current stream)
+    keep: Optional[List[torch.Tensor]] = None       # what its side-stream work reads (run_on_side)
+
+
+_side = _SideState()
+
+
+@contextlib.contextmanager
+def side_scope(stream: Optional[torch.cuda.Stream]):
+    """``run_on_side`` inside this context (on this thread: autograd runs a module's backward on a worker thread of its
+    own) forks onto ``stream``; None keeps everything on the current stream.  On exit, whatever happened inside, the
+    current stream joins ``stream`` (``join_side``), the scope's keep-alive list is dropped and the enclosing scope is
+    current again."""
+    prev = _side.stream, _side.keep
+    _side.stream, _side.keep = stream, []
+    try:
+        yield
+    finally:
+        try:
+            join_side(stream)
+        finally:
+            _side.stream, _side.keep = prev
+
+
+def current_side() -> Optional[torch.cuda.Stream]:
+    return _side.stream
 
 
 def run_on_side(fn, keep=()) -> None:
     """fn() on the side stream, ordered after everything enqueued on the current stream so far.  ``keep``: tensors the
-    side-stream work reads that nothing else holds on to; they stay referenced until ``join_side`` has made the compute
-    stream wait for the side stream, so the caching allocator cannot hand their memory out before the work has run.
-    (``Tensor.record_stream`` would do too, but its blocks only return to the pool once the allocator has polled the
-    side stream's events: with the host a step ahead of the GPU the pool grew by a hipMalloc -- a device
+    side-stream work reads that nothing else holds on to; they stay referenced until the scope's exit has made the
+    compute stream wait for the side stream, so the caching allocator cannot hand their memory out before the work has
+    run.  (``Tensor.record_stream`` would do too, but its blocks only return to the pool once the allocator has polled
+    the side stream's events: with the host a step ahead of the GPU the pool grew by a hipMalloc -- a device
     synchronisation -- every other step, 11 -> 21 GB over 100 steps.)"""
-    side = side_stream
+    side = _side.stream
     if side is None:
         fn()
         return
@@ -330,19 +384,13 @@ def run_on_side(fn, keep=()) -> None:
     with torch.cuda.stream(side):
         side.wait_event(ev)
         fn()
-    _side_keep.extend(t for t in keep if t is not None)
+    _side.keep.extend(t for t in keep if t is not None)
 
 
-_side_keep: List[torch.Tensor] = []
-
-
-def join_side(side: Optional[torch.cuda.Stream] = None) -> None:
-    """The current stream waits for the side stream's work so far (before Adam reads the gradients); what that work
-    read may be freed from here on."""
-    s = side if side is not None else side_stream
-    if s is not None:
-        torch.cuda.current_stream().wait_stream(s)
-    _side_keep.clear()
+def join_side(side: Optional[torch.cuda.Stream]) -> None:
+    """The current stream waits for the side stream's work so far (before Adam reads the gradients)."""
+    if side is not None:
+        torch.cuda.current_stream().wait_stream(side)
 
 
 def _g(grads: Dict[str, torch.Tensor], name: str) -> torch.Tensor:

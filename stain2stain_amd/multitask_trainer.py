@@ -24,7 +24,7 @@ import torch.distributed as dist
 from . import engine, ops
 from .components import FlowMatchingDecoder, SegmentationDecoder, SharedEncoder
 from .ddp import all_reduce_mean_scalar
-from .pix2pix_engine import FlatParams
+from .fused_step import FlatParams
 
 
 def _layer_groups(named: Dict[str, torch.nn.Parameter], prefix: str, owner: str) -> List[List[Tuple[str, torch.nn.Parameter]]]:
@@ -93,30 +93,15 @@ class MultiTaskTrainer:
         self.grads_seg = {k[len("seg_decoder."):]: v for k, v in gr.items() if k.startswith("seg_decoder.")}
         from .ddp import broadcast_from_rank0
         broadcast_from_rank0([b for m in (encoder, flow_decoder, seg_decoder) for b in m.buffers()], process_group)
-        # one launch re-packs every MFMA conv's weights (in fp32 mode all but the stem, which reads the master directly)
-        blocks = list(encoder._blocks) + list(flow_decoder.up_blocks) + list(seg_decoder.up_blocks)
-        self._packed = [cb for pair in blocks for cb in pair if cb is not encoder._blocks[0][0] or
-                        (self._dtype == torch.bfloat16 and cb.cin <= 8)]     # (the bf16 stem runs as a packed conv too)
-        rows, start = [], 0
-        for cb in self._packed:
-            wf, wd = cb.ensure_buffers(self._dtype)
-            rows.append([cb.conv.weight.data_ptr(), wf.data_ptr(), wd.data_ptr(), cb.cout, cb.cin, start])
-            start += ((cb.cout + 31) // 32) * ((cb.cin + 31) // 32)
-        self._pack_desc = torch.tensor(rows, dtype=torch.int64, device=dev)
-        self._pack_total = start
+        self.packer = engine.Conv3x3Packer(list(encoder._blocks) + list(flow_decoder.up_blocks)
+                                           + list(seg_decoder.up_blocks), self._dtype)
         self._side = ops.side_stream_for(dev)
         self.overlap_wgrad = True
         self._group = 0
-        self._repack()
 
     @property
     def step_count(self) -> int:
         return self.fp.step_count
-
-    def _repack(self) -> None:
-        ops.pack_conv3x3_batched(self._pack_desc, self._pack_total, self._dtype)
-        for cb in self._packed:
-            cb.mark_packed(self._dtype)
 
     def _group_done(self) -> None:
         self.fp.bucketer.mark_ready_ordered(self._group, self._side if self.overlap_wgrad else None)
@@ -161,8 +146,7 @@ class MultiTaskTrainer:
         total = flow + w * seg3[0]                                       # (two device scalars: the logged total, :249)
         self.fp.bucketer.start_step()
         self._group = 0
-        engine.side_stream = self._side if self.overlap_wgrad else None
-        try:
+        with engine.side_scope(self._side if self.overlap_wgrad else None):
             L = len(f1) - 1
             dbs, dss, _ = engine.decoder_backward(sdec, dctx_s, dz, self.grads_seg, on_group_done=self._group_done)
             dbf, dsf, _ = engine.decoder_backward(fdec, dctx_f, None, self.grads_flow, g_head=g_head,
@@ -171,9 +155,6 @@ class MultiTaskTrainer:
             engine.encoder_backward(enc._blocks, ectx2, [dss[L - 1 - l] for l in range(L)] + [dbs], self.grads_enc)
             engine.encoder_backward(enc._blocks, ectx1, [dsf[L - 1 - l] for l in range(L)] + [dbf], self.grads_enc,
                                     accumulate=True, on_group_done=self._group_done)
-        finally:
-            engine.side_stream = None
-        engine.join_side(self._side)
         second = "seg_ce" if self.num_classes is not None else "seg_bce"
         losses = {"total": total, "flow": flow, "seg": seg3[0], "seg_dice": seg3[1], second: seg3[2]}
         return losses, ({"v": v, "logits": logits} if want_outputs else None)
@@ -181,7 +162,7 @@ class MultiTaskTrainer:
     def optimizer_step(self) -> None:
         engine.join_side(self._side)
         self.fp.adam(self.lr, self.betas, self.eps, self.wd)
-        self._repack()
+        self.packer.repack()
         engine.mutation_epoch[0] += 1
 
     def step(self, source: torch.Tensor, target: torch.Tensor, mask: torch.Tensor,

@@ -8,6 +8,7 @@ RuntimeError (the reference's only error convention is Python exceptions, src/ut
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import sys
@@ -152,7 +153,19 @@ def _workspace(device: torch.device, numel: int, tag: str) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------------
 _PROFILE: Optional[list] = None
 _PROFILE_ONLY: Optional[set] = None
-PROFILE_TAG = ""          # set by the engines around a network's passes ("G" / "D"): bench.py attributes brackets by it
+PROFILE_TAG = ""          # set by the engines around a network's passes (profile_tag): bench.py attributes brackets by it
+
+
+@contextlib.contextmanager
+def profile_tag(tag: str):
+    """Launches timed inside are named "<op>@<tag>" (the pix2pix engine tags its generator / discriminator passes "G" /
+    "D"); the previous tag is restored on exit, whatever happened inside."""
+    global PROFILE_TAG
+    prev, PROFILE_TAG = PROFILE_TAG, tag
+    try:
+        yield
+    finally:
+        PROFILE_TAG = prev
 
 
 def profile_start(only=None) -> None:

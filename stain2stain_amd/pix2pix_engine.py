@@ -19,7 +19,7 @@ convolution is a 2x2 convolution over the space-to-depth image of its padded inp
 loop with flipped taps (conv3x3_mfma.hip, convkxk).  The skip connections never materialise ``torch.cat``: the encoder's
 norm pass writes relu(z) into the first half of the decoder's concatenation buffer and the decoder's norm pass writes its
 output into the second half.  Parameters, gradients and Adam moments of each network live in flat fp32 buffers in
-backward-completion order (``trainer.FlatParams``), so gradient buckets are contiguous slices.
+backward-completion order (``fused_step.FlatParams``), so gradient buckets are contiguous slices.
 """
 from __future__ import annotations
 
@@ -31,7 +31,8 @@ import torch
 import torch.distributed as dist
 
 from . import engine, ops
-from .ddp import ALIGN, GradBucketer, all_reduce_mean_scalar, broadcast_from_rank0
+from .ddp import all_reduce_mean_scalar
+from .fused_step import CapturedStep, FlatParams
 from .pix2pix import PatchGANDiscriminator, Pix2PixGenerator
 
 LRELU = 0.2
@@ -48,96 +49,6 @@ def _check_norms(net) -> None:
         if isinstance(m, InstanceNormLeakyReLU) and (abs(m.eps - 1e-5) > 1e-12 or m.weight is not None):
             raise NotImplementedError(f"stain2stain_amd: {name}: the fused pix2pix passes implement "
                                       "InstanceNorm2d(affine=False, eps=1e-5) only")
-
-
-class FlatParams:
-    """Parameters of one network as views of a flat fp32 buffer + flat gradient / Adam-moment buffers.
-
-    ``groups``: [[(name, parameter), ...], ...] in the order the backward pass completes them."""
-
-    def __init__(self, groups: List[List[Tuple[str, torch.nn.Parameter]]], bucket_mb: float, process_group,
-                 max_bucket_mb: float = 16.0, sharded: bool = False):
-        dev = groups[0][0][1].device
-        sizes, offs, off = [], {}, 0
-        self.group_range: List[Tuple[int, int]] = []
-        for g in groups:
-            start = off
-            for name, p in g:
-                offs[name] = off
-                off += (p.numel() + 7) // 8 * 8            # 32-byte aligned views
-            off = (off + ALIGN - 1) // ALIGN * ALIGN       # groups (layers) divide into aligned shards for <= 8 ranks
-            sizes.append(off - start)
-            self.group_range.append((start, off))
-        self.p = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.g = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.m = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.v = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.grads: Dict[str, torch.Tensor] = {}
-        self.slot: Dict[str, Tuple[int, int]] = {}
-        with torch.no_grad():
-            for g in groups:
-                for name, p in g:
-                    o, n = offs[name], p.numel()
-                    self.p[o:o + n].copy_(p.detach().reshape(-1))
-                    p.data = self.p[o:o + n].view(p.shape)
-                    p.grad = self.g[o:o + n].view(p.shape)
-                    self.grads[name] = p.grad
-                    self.slot[name] = (o, n)
-        self.bucketer = GradBucketer(self.g, sizes, bucket_mb, process_group, max_bucket_mb,
-                                     "reduce_scatter" if sharded else "allreduce")
-        self.step_count = 0
-        broadcast_from_rank0([self.p], process_group)
-
-    def adam(self, lr: float, betas: Tuple[float, float], eps: float, weight_decay: float,
-             hyper_dev: Optional[torch.Tensor] = None) -> None:
-        """``hyper_dev``: the Adam scalars in device memory (a captured step; the caller advances ``step_count`` and
-        refreshes them before each replay) instead of kernel arguments."""
-        self.bucketer.wait_all()
-        if hyper_dev is None:
-            self.step_count += 1
-        for lo, hi in self.bucketer.shards():              # everything, or this rank's slices in sharded mode
-            if hyper_dev is None:
-                ops.adam_step_(self.p[lo:hi], self.g[lo:hi], self.m[lo:hi], self.v[lo:hi], self.step_count, lr, betas[0],
-                               betas[1], eps, weight_decay, self.bucketer.grad_scale)
-            else:
-                ops.adam_step_dev_(self.p[lo:hi], self.g[lo:hi], self.m[lo:hi], self.v[lo:hi], hyper_dev)
-        self.bucketer.all_gather(self.p)
-
-    def adam_group(self, group: int, lr: float, betas: Tuple[float, float], eps: float, weight_decay: float,
-                   hyper_dev: Optional[torch.Tensor] = None) -> None:
-        """Adam on the slice of parameter group ``group`` alone (the step counter is the caller's: ``begin_step``), for
-        the update-in-backward of a trainer without a gradient exchange.  Adam is element-wise: the slices of all groups
-        together are exactly ``adam``."""
-        lo, hi = self.group_range[group]
-        if hyper_dev is None:
-            ops.adam_step_(self.p[lo:hi], self.g[lo:hi], self.m[lo:hi], self.v[lo:hi], self.step_count, lr, betas[0],
-                           betas[1], eps, weight_decay, self.bucketer.grad_scale)
-        else:
-            ops.adam_step_dev_(self.p[lo:hi], self.g[lo:hi], self.m[lo:hi], self.v[lo:hi], hyper_dev)
-
-    def state_dict(self) -> Dict:
-        """Adam state by parameter name.  Sharded optimiser: the moments are all-gathered first (a collective: every rank
-        calls), so the dump is complete on every rank."""
-        if self.bucketer.mode == "reduce_scatter" and self.bucketer.enabled and self.step_count > 0:
-            self.bucketer.all_gather(self.m)
-            self.bucketer.all_gather(self.v)
-        out = {"step": self.step_count, "exp_avg": {}, "exp_avg_sq": {}}
-        for name, (o, n) in self.slot.items():
-            shape = self.grads[name].shape
-            out["exp_avg"][name] = self.m[o:o + n].view(shape).clone()
-            out["exp_avg_sq"][name] = self.v[o:o + n].view(shape).clone()
-        return out
-
-    def load_state_dict(self, sd: Dict) -> None:
-        if set(sd["exp_avg"]) != set(self.slot) or set(sd["exp_avg_sq"]) != set(self.slot):
-            raise ValueError("optimizer state does not match this network's parameters")
-        for name, (o, n) in self.slot.items():
-            for buf, key in ((self.m, "exp_avg"), (self.v, "exp_avg_sq")):
-                t = sd[key][name]
-                if tuple(t.shape) != tuple(self.grads[name].shape):
-                    raise ValueError(f"optimizer state {name}: shape {tuple(t.shape)} != {tuple(self.grads[name].shape)}")
-                buf[o:o + n].copy_(t.reshape(-1))
-        self.step_count = int(sd["step"])
 
 
 @dataclass
@@ -272,7 +183,7 @@ class Pix2PixTrainer:
                  sync_loss: bool = True, max_bucket_mb: float = 16.0, sharded_optimizer: bool = False,
                  graph: bool = False):
         """``graph``: ``step()`` replays one captured hipGraph per G + D step (~200 launches on two streams); the first
-        step of a batch shape runs eagerly, the second captures; bit-equal to the eager step (see CFMTrainer)."""
+        step of a batch shape runs eagerly, the second captures; bit-equal to the eager step (fused_step.CapturedStep)."""
         dev = next(G.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("stain2stain_amd: Pix2PixTrainer needs the networks on a GPU (HIP-only implementation)")
@@ -313,8 +224,9 @@ class Pix2PixTrainer:
         self.opt_in_backward = os.environ.get("S2S_P2P_OPT_IN_BWD", "0") == "1"
         self.last: Dict[str, torch.Tensor] = {}
         self.graph = graph
-        self._captured, self._warm_key = None, None
-        self._hyper = None                     # ops.AdamHyperRing, created with the first captured step
+        self._graph_step = CapturedStep()
+
+    _captured = property(lambda self: self._graph_step.graph)      # of the current batch shapes (None: not captured)
 
     def optimizer_state_dict(self) -> Dict:
         """Both Adam states (by parameter name) + hyper-parameters; a collective with ``sharded_optimizer`` (FlatParams.state_dict)."""
@@ -331,11 +243,7 @@ class Pix2PixTrainer:
     def _mark(self, fp: FlatParams, group: int) -> None:
         """Group ``group`` of ``fp`` has its gradients enqueued (bias gradients on the compute stream, the weight gradient
         on the side stream): exchange the buckets it closes, ordered behind both streams."""
-        fp.bucketer.mark_ready_ordered(group, engine.side_stream)
-
-    def _join(self) -> None:
-        engine.join_side()
-        engine.side_stream = None
+        fp.bucketer.mark_ready_ordered(group, engine.current_side())
 
     # ------------------------------------------------------------------------------------------------------------
     # generator
@@ -408,13 +316,10 @@ class Pix2PixTrainer:
 
     def _update_group(self, grp: int, l: _Layer, hyper_dev) -> None:
         """Adam + repack of generator layer ``l`` (parameter group ``grp``), behind its gradients on both streams."""
-        side = engine.side_stream
-        if side is None:
-            self.pG.adam_group(grp, self.lr, self.betas, self.eps, self.wd, hyper_dev)
-            self.packG.repack_layer(l.name)
-            return
-        side.wait_stream(torch.cuda.current_stream())     # bias gradient; the data gradient that reads the packed operand
-        with torch.cuda.stream(side):
+        side = engine.current_side()
+        if side is not None:
+            side.wait_stream(torch.cuda.current_stream())     # bias gradient; the data gradient that reads the packed operand
+        with torch.cuda.stream(side):                         # (None: the current stream)
             self.pG.adam_group(grp, self.lr, self.betas, self.eps, self.wd, hyper_dev)
             self.packG.repack_layer(l.name)
 
@@ -559,42 +464,40 @@ class Pix2PixTrainer:
         dev, dt = src.device, self.dtype
         src, tgt = src.contiguous().float(), tgt.contiguous().float()
         losses = torch.zeros((8,), dtype=torch.float32, device=dev)
-        ops.PROFILE_TAG = "G"
-        gctx = self.g_forward(src)
-        ops.PROFILE_TAG = "D"
-        d_in = torch.empty((2 * B, H, W, 8), dtype=dt, device=dev)          # [real pairs | fake pairs]
-        ops.p2p_pack_input(src, tgt, d_in[:B])
-        fake = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if want_fake else None
-        ops.p2p_tanh_l1_fwd(gctx.h, src, tgt, d_in[B:], fake, l1_out=losses[4:5])
-        # ---- discriminator update: real and detached fake as one batch of 2B samples ----
-        z, saved = self.d_forward(d_in)
-        npatch = z.shape[1] * z.shape[2]
-        _, dz = ops.p2p_bce_logits(z, B, 0.5 / (B * npatch), 0.5 / (B * npatch), out=losses[0:2])
-        engine.side_stream = self._side if self.overlap_wgrad else None
-        self.d_backward(saved, dz, want_w=True, need_input_grad=False)
-        self._join()
-        if update:
-            self.pD.adam(self.lr, self.betas, self.eps, self.wd, hyper_dev)
-            self.packD.repack()
-            zg, saved_g = self.d_forward(d_in[B:])                          # through the UPDATED discriminator
-        else:
-            self.pD.bucketer.wait_all()
-            zg, saved_g = z[B:], [tuple(None if t is None else self._second_half(t, B) for t in lay) for lay in saved]
-        # ---- generator update ----
-        _, dzg = ops.p2p_bce_logits(zg, B, 1.0 / (B * npatch), 0.0, out=losses[2:4])
-        gd = self.d_backward(saved_g, dzg, want_w=False, need_input_grad=True)
-        dh = ops.p2p_tanh_l1_bwd(gctx.h, tgt, gd, self.lambda_l1 / (B * C * H * W))
-        ops.PROFILE_TAG = "G"
-        engine.side_stream = self._side if self.overlap_wgrad else None
-        in_bwd = update and self.opt_in_backward and not self.pG.bucketer.enabled
-        self.g_backward(gctx, dh, update=in_bwd, hyper_dev=hyper_dev)
-        self._join()
-        if update and not in_bwd:
-            self.pG.adam(self.lr, self.betas, self.eps, self.wd, hyper_dev)
-            self.packG.repack()
-        elif not update:
-            self.pG.bucketer.wait_all()
-        ops.PROFILE_TAG = ""
+        side = self._side if self.overlap_wgrad else None
+        with ops.profile_tag("G"):
+            gctx = self.g_forward(src)
+        with ops.profile_tag("D"):
+            d_in = torch.empty((2 * B, H, W, 8), dtype=dt, device=dev)          # [real pairs | fake pairs]
+            ops.p2p_pack_input(src, tgt, d_in[:B])
+            fake = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if want_fake else None
+            ops.p2p_tanh_l1_fwd(gctx.h, src, tgt, d_in[B:], fake, l1_out=losses[4:5])
+            # ---- discriminator update: real and detached fake as one batch of 2B samples ----
+            z, saved = self.d_forward(d_in)
+            npatch = z.shape[1] * z.shape[2]
+            _, dz = ops.p2p_bce_logits(z, B, 0.5 / (B * npatch), 0.5 / (B * npatch), out=losses[0:2])
+            with engine.side_scope(side):
+                self.d_backward(saved, dz, want_w=True, need_input_grad=False)
+            if update:
+                self.pD.adam(self.lr, self.betas, self.eps, self.wd, hyper_dev)
+                self.packD.repack()
+                zg, saved_g = self.d_forward(d_in[B:])                          # through the UPDATED discriminator
+            else:
+                self.pD.bucketer.wait_all()
+                zg, saved_g = z[B:], [tuple(None if t is None else self._second_half(t, B) for t in lay) for lay in saved]
+            # ---- generator update ----
+            _, dzg = ops.p2p_bce_logits(zg, B, 1.0 / (B * npatch), 0.0, out=losses[2:4])
+            gd = self.d_backward(saved_g, dzg, want_w=False, need_input_grad=True)
+            dh = ops.p2p_tanh_l1_bwd(gctx.h, tgt, gd, self.lambda_l1 / (B * C * H * W))
+        with ops.profile_tag("G"):
+            in_bwd = update and self.opt_in_backward and not self.pG.bucketer.enabled
+            with engine.side_scope(side):
+                self.g_backward(gctx, dh, update=in_bwd, hyper_dev=hyper_dev)
+            if update and not in_bwd:
+                self.pG.adam(self.lr, self.betas, self.eps, self.wd, hyper_dev)
+                self.packG.repack()
+            elif not update:
+                self.pG.bucketer.wait_all()
         return losses, fake
 
     @staticmethod
@@ -613,7 +516,9 @@ class Pix2PixTrainer:
         (rank means when ``sync_loss``), still on the device."""
         with ops.workspace_owner(self):          # split-K / weight-gradient slabs belong to this trainer (ops._workspace)
             if self.graph and ops._PROFILE is None:
-                return self._step_graphed(src, tgt)
+                return self._graph_step.run((tuple(src.shape), tuple(tgt.shape), src.device, self.overlap_wgrad),
+                                            (src, tgt), self._step_body, [self.pG, self.pD],
+                                            (self.lr, self.betas, self.eps, self.wd))
             return self._step_body(src, tgt, None)
 
     def _step_body(self, src, tgt, hyper_dev) -> torch.Tensor:
@@ -625,38 +530,9 @@ class Pix2PixTrainer:
                 ops.axpy_(losses, losses, 1.0 / dist.get_world_size(self.pg) - 1.0)     # x += (1/w - 1) x
         return losses
 
-    def _step_graphed(self, src: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
-        key = (tuple(src.shape), tuple(tgt.shape), src.device, self.overlap_wgrad)
-        if self.pG.bucketer.enabled and dist.get_backend(self.pg) != "nccl":
-            raise RuntimeError("stain2stain_amd: graph=True captures the gradient exchange; only RCCL ('nccl') "
-                               "collectives can be captured")
-        if self._hyper is None:
-            self._hyper = ops.AdamHyperRing(src.device)
-        if self._captured is None or self._captured[0] != key:
-            if self._warm_key != key:       # first step of this shape: eager (module load, LDS attributes, workspaces)
-                self._warm_key, self._captured = key, None
-                return self._step_body(src, tgt, None)
-            s_src = torch.empty_like(src, dtype=torch.float32).contiguous()
-            s_tgt = torch.empty_like(tgt, dtype=torch.float32).contiguous()
-            graph = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize()
-            with ops.capture_graph(graph):
-                losses = self._step_body(s_src, s_tgt, self._hyper.dev)
-            self._captured = (key, graph, s_src, s_tgt, losses)
-        _, graph, s_src, s_tgt, losses = self._captured
-        s_src.copy_(src); s_tgt.copy_(tgt)
-        self.pD.step_count += 1
-        self.pG.step_count += 1
-        if self.pD.step_count != self.pG.step_count:
-            raise RuntimeError("graph=True: the two optimisers must have taken the same number of steps")
-        self._hyper.push(ops.adam_hyper(self.pG.step_count, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                                        self.pG.bucketer.grad_scale))
-        graph.replay()
-        return losses.clone()
-
     def close(self) -> None:
         """Drop the captured graph, its static buffers and the pinned Adam-scalar ring now (see CFMTrainer.close)."""
-        self._captured, self._warm_key, self._hyper = None, None, None
+        self._graph_step.close()
         ops.release_workspaces(self)
 
     def __del__(self):
