@@ -245,6 +245,31 @@ int s2s_seg_loss(const float* z, const float* g, float* dz, float* out, double* 
 int s2s_seg_loss_multiclass(const float* z, const long* target, float* dz, float* out, double* work, long B, long HW,
                             int C, int ignore_index, float smooth, float dice_weight, float grad_scale, void* stream);
 
+/* ---- evaluation passes (eval_metrics.hip): losses without gradients + segmentation metrics -----------------
+ * Validation / test steps of the multitask modules.  Per-workgroup partials and a one-workgroup finalize: no atomics,
+ * bit-reproducible, no allocation or host synchronisation (capturable).
+ * Binary (conditional_flow_matching_multitask.py:326-343, 366-381): z, g: float[n] (logits, {0,1} mask);
+ *   out: float[5] = {seg, dice loss, bce, dice_coef, iou}, the first three as s2s_seg_loss gives them;
+ *   counts: int64[4] = {I, P, G, U} of pred = sigmoid(z) > 0.5 (I = sum pred*g, P = sum pred, G = sum g,
+ *   U = sum (pred | g)); dice_coef = (2I + 1e-7) / (P + G + 1e-7), iou = (I + 1e-7) / (U + 1e-7) in fp32.
+ *   The predicate is the loss kernel's p = 1/(1+exp(-z)) > 0.5; it differs from z > 0 for 0 < z <~ 1e-7.
+ *   work: double[512*8].
+ * Multiclass (conditional_flow_matching_multitask_multiclassloss.py:437-470): z: float[B][C][HW], target: int64[B][HW],
+ *   2 <= C <= 8; out: float[5] = {seg, dice loss, ce, mean dice_coef, mean iou} (first three as
+ *   s2s_seg_loss_multiclass); pred = argmax_c z (first maximal index); counts: int64[32] = I_c, P_c, G_c, U_c at
+ *   [0|8|16|24 + c] (P_c counts every pixel, ignored targets included); the means run over c != ignore_index.
+ *   work: double[512*58].
+ * Flow head + MSE (task_decoders.py:132 + conditional_flow_matching.py:72), forward only: loss = mean((W a + b - u)^2)
+ *   over the NHWC activation x (C % 8 == 0, ld % 8 == 0, bf16 or fp32) and u: float[B][Cout][H][W], Cout <= 8;
+ *   lpart: double[s2s_head_mse_eval_blocks()]. */
+int s2s_seg_eval_binary(const float* z, const float* g, float* out, long* counts, double* work, long n, float smooth,
+                        float dice_weight, void* stream);
+int s2s_seg_eval_multiclass(const float* z, const long* target, float* out, long* counts, double* work, long B,
+                            long HW, int C, int ignore_index, float smooth, float dice_weight, void* stream);
+int s2s_head_mse_eval_blocks(int B, int H, int W, int C);
+int s2s_head_mse_eval(int dtype, const void* x, int ldx, const float* w, const float* bias, const float* u_nchw,
+                      float* loss, double* lpart, int B, int H, int W, int C, int Cout, void* stream);
+
 /* ---- loss variants and class conditioning (loss_variants.hip) -- SURVEY section 8 row f4 -----------------
  * ROI-weighted MSE (conditional_flow_matching_masked.py:76-90): w = 1 + roi_lambda * mask,
  *   out[0] = sum(w (v-u)^2) / (sum(w) + 1e-8), w broadcast over C.  v, u: float[B][C][HW]; mask: float[B][HW];

@@ -19,7 +19,7 @@ from typing import Any, Dict, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import evaluation, ops
 
 try:  # pragma: no cover - Lightning is not installed in the build image
     from lightning import LightningModule as _Base
@@ -582,6 +582,46 @@ class MultiTaskFlowMatchingModule(_Base):
         for k, v in d.items():
             self.log(f"train/{k}_loss", v, on_step=True, on_epoch=True, prog_bar=(k == "total"), sync_dist=True)
         return loss
+
+    # the reference's validation / test logging: (key suffix, value key, prog_bar); every call is on_step=False,
+    # on_epoch=True, sync_dist=True (conditional_flow_matching_multitask.py:306-343, 359-381,
+    # conditional_flow_matching_multitask_multiclassloss.py:348-371, 424-476)
+    _LOSS_KEYS = (("loss", "total", True), ("flow_loss", "flow", False), ("seg_loss", "seg", True))
+    _METRIC_KEYS = (("dice_coef", "dice_coef", True), ("iou", "iou", True))
+
+    def _log_keys(self, stage: str):
+        keys = list(self._LOSS_KEYS)
+        if stage == "val":
+            second = "seg_ce" if self.num_classes is not None else "seg_bce"
+            keys += [("seg_dice", "seg_dice", False), (second, second, False)]
+            if self.num_classes is None:         # the multiclass reference has its validation metrics commented out
+                keys += list(self._METRIC_KEYS)
+        else:
+            keys += list(self._METRIC_KEYS)
+        return keys
+
+    def evaluation_values(self, batch) -> Dict[str, torch.Tensor]:
+        """Every value of the validation / test steps for one batch as device scalars: {"total", "flow", "seg",
+        "seg_dice", "seg_bce" | "seg_ce", "dice_coef", "iou"}.  The networks run in the mode they are in (Lightning sets
+        eval mode: BatchNorm from the running statistics), through the forward-only head + MSE and segmentation
+        metric kernels; the mask head runs once (the reference's second forward_segmentation is the same in eval mode)."""
+        source_img, target_img, gt_mask = batch
+        with evaluation.eval_grad_mode():
+            t, xt, ut = self.flow_matcher.sample_location_and_conditional_flow(source_img, target_img)
+            return evaluation.multitask_values(
+                self.encoder, self.flow_decoder, self.seg_decoder, self.time_embedding.dim, source_img, xt, t, ut,
+                gt_mask, self.num_classes, self.ignore_index, self.dice_smooth, self.dice_weight, self.seg_loss_weight)
+
+    def _eval_step(self, batch, stage: str) -> None:
+        d = self.evaluation_values(batch)
+        for suffix, key, bar in self._log_keys(stage):
+            self.log(f"{stage}/{suffix}", d[key], on_step=False, on_epoch=True, prog_bar=bar, sync_dist=True)
+
+    def validation_step(self, batch, batch_idx: int) -> None:
+        self._eval_step(batch, "val")
+
+    def test_step(self, batch, batch_idx: int) -> None:
+        self._eval_step(batch, "test")
 
     def configure_optimizers(self) -> Dict[str, Any]:
         params = (list(self.encoder.parameters()) + list(self.flow_decoder.parameters())

@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
-from . import engine, ops
+from . import engine, evaluation, ops
 from .components import FlowMatchingDecoder, SegmentationDecoder, SharedEncoder
 from .ddp import all_reduce_mean_scalar
 from .fused_step import FlatParams
@@ -98,6 +98,7 @@ class MultiTaskTrainer:
         self._side = ops.side_stream_for(dev)
         self.overlap_wgrad = True
         self._group = 0
+        self._eval_owner = object()         # evaluate()'s workspaces, released by close()
 
     @property
     def step_count(self) -> int:
@@ -176,3 +177,40 @@ class MultiTaskTrainer:
             work.wait()
             total = total / dist.get_world_size(self.pg)
         return total
+
+    def evaluate(self, source: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, t: Optional[torch.Tensor] = None,
+                 accumulator: Optional[evaluation.EvalAccumulator] = None) -> Dict[str, torch.Tensor]:
+        """The validation / test values of one batch as device scalars: {"loss", "flow_loss", "seg_loss", "seg_dice",
+        "seg_bce" | "seg_ce", "dice_coef", "iou"} (the reference's logging suffixes; dice_coef / iou as its test_step
+        computes them, per-class means in the multiclass form).  Path sample, eval-mode forward of both heads
+        (BatchNorm from the running statistics), forward-only head + MSE, one-pass segmentation loss + metrics.  Touches
+        no training state, never waits for the device, runs no collective (``accumulator.compute()`` does, once) and
+        uses workspaces of its own.  ``accumulator``: the batch is added to it with weight ``source.shape[0]``."""
+        with ops.workspace_owner(self._eval_owner), evaluation.eval_grad_mode():
+            x0, x1 = source.float().contiguous(), target.float().contiguous()
+            if t is None:
+                t = torch.rand(x0.shape[0], device=x0.device, dtype=torch.float32)
+            t = t.float().contiguous()
+            eps_noise = torch.randn_like(x0) if self.sigma != 0.0 else None
+            xt, ut = ops.cfm_sample(x0, x1, t, self.sigma, eps_noise)
+            enc, fdec, sdec = self.encoder, self.flow_decoder, self.seg_decoder
+            flow = evaluation.flow_loss(enc, fdec, self.time_emb_dim, xt, t, ut)
+            logits = evaluation.mask_logits(enc, sdec, x0)
+            d = evaluation.segmentation_values(logits, mask, self.num_classes, self.ignore_index, self.dice_smooth,
+                                               self.dice_weight)
+            second = "seg_ce" if self.num_classes is not None else "seg_bce"
+            out = {"loss": flow + float(self.seg_loss_weight) * d["seg"], "flow_loss": flow, "seg_loss": d["seg"],
+                   "seg_dice": d["seg_dice"], second: d[second], "dice_coef": d["dice_coef"], "iou": d["iou"]}
+        if accumulator is not None:
+            accumulator.add(out, x0.shape[0])
+        return out
+
+    def close(self) -> None:
+        """Release evaluate()'s workspaces."""
+        ops.release_workspaces(self._eval_owner)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass

@@ -692,6 +692,112 @@ def seg_loss_multiclass(z: torch.Tensor, target: torch.Tensor, ignore_index: int
     return out, dz
 
 
+# ------------------------------------------------------------------------------------------------
+# evaluation passes (validation / test): losses without gradients + segmentation metrics
+# ------------------------------------------------------------------------------------------------
+EV_BLOCKS = 512
+
+
+def _gpu_f32_operand(t: torch.Tensor, what: str) -> torch.Tensor:
+    if not t.is_cuda:
+        raise RuntimeError(f"stain2stain_amd: {what} is not on the GPU (there is no CPU path)")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"stain2stain_amd: {what} must be float32, got {t.dtype}")
+    return t.contiguous()
+
+
+def _binary_mask(g: torch.Tensor) -> torch.Tensor:
+    if g.dtype in (torch.bool, torch.uint8):
+        return g.to(torch.float32).contiguous()
+    if g.dtype != torch.float32:
+        raise RuntimeError(f"stain2stain_amd: mask must be float32 (0/1), uint8 or bool, got {g.dtype}")
+    return g.contiguous()
+
+
+@_timed("seg_eval_binary")
+def seg_eval_binary(z: torch.Tensor, g: torch.Tensor, smooth: float = 1.0, dice_weight: float = 0.5):
+    """Loss values and thresholded metrics of the binary mask head, one pass, no gradient.  ``z``: logits [B,1,H,W]
+    fp32; ``g``: mask of z's shape ([B,H,W] accepted), fp32 0/1, uint8 or bool.  Returns (out, counts): out = fp32[5]
+    {seg, dice loss, bce, dice_coef, iou}, counts = int64[4] {I, P, G, U} of pred = sigmoid(z) > 0.5."""
+    if z.dim() != 4 or z.shape[1] != 1:
+        raise RuntimeError(f"stain2stain_amd: seg_eval_binary wants logits [B,1,H,W], got {tuple(z.shape)}")
+    if g.dim() == 3:
+        g = g.unsqueeze(1)
+    if tuple(g.shape) != tuple(z.shape):
+        raise RuntimeError(f"stain2stain_amd: mask shape {tuple(g.shape)} does not match logits {tuple(z.shape)}")
+    if g.device != z.device:
+        raise RuntimeError("stain2stain_amd: logits and mask are on different devices")
+    z, g = _gpu_f32_operand(z, "logits"), _binary_mask(g)
+    out = torch.empty((5,), dtype=torch.float32, device=z.device)
+    counts = torch.empty((4,), dtype=torch.int64, device=z.device)
+    work = _workspace(z.device, 2 * EV_BLOCKS * 8, "seg_eval").view(torch.float64)
+    _native.check(_L().s2s_seg_eval_binary(_f32(z), _f32(g), _f32(out), counts.data_ptr(), work.data_ptr(), z.numel(),
+                                           float(smooth), float(dice_weight), _stream()), "seg_eval_binary")
+    return out, counts
+
+
+@_timed("seg_eval_multiclass")
+def seg_eval_multiclass(z: torch.Tensor, target: torch.Tensor, ignore_index: int = -100, smooth: float = 1.0,
+                        dice_weight: float = 0.5):
+    """Loss values and per-class metrics of the multiclass mask head, one pass, no gradient, no host sync.  ``z``:
+    logits [B,C,H,W] fp32, 2 <= C <= 8; ``target``: class indices [B,H,W] or [B,1,H,W] (any integer dtype).  Returns
+    (out, counts): out = fp32[5] {seg, dice loss, ce, mean dice_coef, mean iou over c != ignore_index}, counts =
+    int64[4, C] rows I, P, G, U of pred = argmax_c z (first maximal index; P counts ignored pixels too).  Labels
+    outside [0, C) that are not ignore_index contribute nothing (the reference raises in F.one_hot)."""
+    if z.dim() != 4:
+        raise RuntimeError(f"stain2stain_amd: seg_eval_multiclass wants logits [B,C,H,W], got {tuple(z.shape)}")
+    B, C, H, W = z.shape
+    if not 2 <= C <= 8:
+        raise RuntimeError(f"stain2stain_amd: seg_eval_multiclass supports 2 <= C <= 8 classes, got {C}")
+    if target.dim() == 4 and target.shape[1] == 1:
+        target = target[:, 0]
+    if tuple(target.shape) != (B, H, W):
+        raise RuntimeError(f"stain2stain_amd: target shape {tuple(target.shape)} does not match logits {tuple(z.shape)}")
+    if target.dtype.is_floating_point or target.dtype == torch.bool or target.dtype.is_complex:
+        raise RuntimeError(f"stain2stain_amd: target must hold integer class indices, got {target.dtype}")
+    if target.device != z.device:
+        raise RuntimeError("stain2stain_amd: logits and target are on different devices")
+    z = _gpu_f32_operand(z, "logits")
+    target = target.to(torch.int64).contiguous()
+    out = torch.empty((5,), dtype=torch.float32, device=z.device)
+    counts = torch.empty((32,), dtype=torch.int64, device=z.device)
+    work = _workspace(z.device, 2 * EV_BLOCKS * 58, "seg_eval").view(torch.float64)
+    _native.check(_L().s2s_seg_eval_multiclass(_f32(z), target.data_ptr(), _f32(out), counts.data_ptr(),
+                                               work.data_ptr(), B, H * W, C, int(ignore_index), float(smooth),
+                                               float(dice_weight), _stream()), "seg_eval_multiclass")
+    return out, counts.view(4, 8)[:, :C]
+
+
+@_timed("head_mse_eval")
+def head_mse_eval(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], u_nchw: torch.Tensor) -> torch.Tensor:
+    """mean((conv1x1(x; w, bias) - u)^2) as a device scalar, v never stored: the evaluation form of head_fwd +
+    mse_loss.  ``x``: NHWC activation view (bf16 or fp32, C % 8 == 0); ``w``: [Cout, C(,1,1)] fp32, Cout <= 8;
+    ``u_nchw``: [B, Cout, H, W] fp32."""
+    if x.dim() != 4:
+        raise RuntimeError("stain2stain_amd: head_mse_eval wants an NHWC activation [B,H,W,C]")
+    B, H, W, C = x.shape
+    cout = w.shape[0]
+    if w.numel() != cout * C:
+        raise RuntimeError(f"stain2stain_amd: head weight {tuple(w.shape)} does not match {C} input channels")
+    if not 1 <= cout <= 8 or C % 8:
+        raise RuntimeError(f"stain2stain_amd: head_mse_eval supports C % 8 == 0 and 1 <= Cout <= 8 (C={C}, Cout={cout})")
+    if tuple(u_nchw.shape) != (B, cout, H, W):
+        raise RuntimeError(f"stain2stain_amd: target shape {tuple(u_nchw.shape)} != {(B, cout, H, W)}")
+    if bias is not None and bias.numel() != cout:
+        raise RuntimeError("stain2stain_amd: head bias does not match its weight")
+    px, ldx = _nhwc(x)
+    u = _gpu_f32_operand(u_nchw, "flow target")
+    nb = _L().s2s_head_mse_eval_blocks(B, H, W, C)
+    _native.check(nb if nb < 0 else 0, "head_mse_eval_blocks")
+    lpart = _workspace(x.device, 2 * nb, "head_mse_eval").view(torch.float64)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    _native.check(_L().s2s_head_mse_eval(_dt(x), px, ldx, _f32(w.detach().reshape(cout, C).contiguous()),
+                                         _f32(None if bias is None else bias.detach().contiguous()), _f32(u),
+                                         loss.data_ptr(), lpart.data_ptr(), B, H, W, C, cout, _stream()),
+                  "head_mse_eval")
+    return loss
+
+
 def _mask_bhw(mask: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
     B, C, H, W = like.shape
     if mask.dim() == 4 and mask.shape[1] == 1:

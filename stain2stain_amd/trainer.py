@@ -19,7 +19,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
-from . import engine, ops
+from . import engine, evaluation, ops
 from .components import FlowUNet
 from .ddp import all_reduce_mean_scalar, broadcast_from_rank0
 from .fused_step import CapturedStep, FlatParams
@@ -127,6 +127,8 @@ class CFMTrainer:
         self.overlap_wgrad = True       # bench.py clears it on the steps whose kernels it brackets with HIP events
         self.graph = graph
         self._graph_step = CapturedStep()
+        # evaluate()'s workspaces: never the ones a captured training step has baked into its graph (released by close())
+        self._eval_owner = object()
 
     step_count = property(lambda self: self.fp.step_count)
     bucketer = property(lambda self: self.fp.bucketer)
@@ -272,12 +274,34 @@ class CFMTrainer:
             loss = loss / dist.get_world_size(self.pg)
         return loss
 
+    def evaluate(self, x0: torch.Tensor, x1: torch.Tensor, t: Optional[torch.Tensor] = None,
+                 accumulator: Optional[evaluation.EvalAccumulator] = None) -> Dict[str, torch.Tensor]:
+        """The validation loss of one batch, {"loss": device scalar} (conditional_flow_matching.py:88-97): path sample,
+        eval-mode forward (BatchNorm from the running statistics), forward-only head + MSE.  Touches no training state
+        (parameters, running statistics, gradients, Adam moments, step count, packed weights), never waits for the device,
+        runs no collective (``accumulator.compute()`` does that once per epoch) and runs eagerly beside a captured step,
+        on workspaces of its own.  ``accumulator``: the batch is added to it with weight ``x0.shape[0]``."""
+        net = self.net
+        with ops.workspace_owner(self._eval_owner), evaluation.eval_grad_mode():
+            x0, x1 = x0.float().contiguous(), x1.float().contiguous()
+            if t is None:
+                t = torch.rand(x0.shape[0], device=x0.device, dtype=torch.float32)
+            t = t.float().contiguous()
+            eps_noise = torch.randn_like(x0) if self.sigma != 0.0 else None
+            xt, ut = ops.cfm_sample(x0, x1, t, self.sigma, eps_noise)
+            loss = evaluation.flow_loss(net.encoder, net.flow_decoder, net.time_embedding.dim, xt, t, ut)
+        out = {"loss": loss}
+        if accumulator is not None:
+            accumulator.add(out, x0.shape[0])
+        return out
+
     def close(self) -> None:
         """Drop the captured graph, its static buffers and the pinned Adam-scalar ring while torch and the HIP runtime are
         fully alive (a captured step sits in a reference cycle with its trainer; left to the cyclic collector it may be
         destroyed during another capture or at interpreter exit, in an order the runtime does not define)."""
         self._graph_step.close()
         ops.release_workspaces(self)
+        ops.release_workspaces(self._eval_owner)
 
     def __del__(self):
         try:
