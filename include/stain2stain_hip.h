@@ -206,6 +206,21 @@ int s2s_adam_step_dev(float* p, const float* g, float* m, float* v, long n, cons
 long s2s_adam_multi_blocks(long n);
 int s2s_adam_multi(const void* desc, int ntensors, long total, int step, float lr, float beta1, float beta2, float eps,
                    float weight_decay, float grad_scale, void* stream);
+/* Exponential moving average of the weights fused into the flat Adam pass: p, m, v exactly as s2s_adam_step /
+ * s2s_adam_step_dev, then ema = lerp(ema, p_new, ema_weight) on the value just computed (torch.lerp's two-branch form).
+ * ema_weight 1.0 copies (the first update of torch.optim.swa_utils.AveragedModel), 1 - decay averages.  p, g, m, v, ema
+ * must be 16-byte aligned (S2S_ERR_ALIGN otherwise).  The _dev form reads the weight from device memory (*ema_weight),
+ * so a captured step replays it unchanged. */
+int s2s_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, long n, int step, float lr, float beta1,
+                      float beta2, float eps, float weight_decay, float grad_scale, float ema_weight, void* stream);
+int s2s_adam_ema_step_dev(float* p, const float* g, float* m, float* v, float* ema, long n, const float* hyper,
+                          const float* ema_weight, void* stream);
+/* dst = lerp(dst, src, *weight) over a list of tensors in one launch (BatchNorm buffers of the fused trainers, every
+ * parameter and buffer of stain2stain_amd.FusedEMA): desc = device long[ntensors][5] {dst, src, n, first block, kind},
+ * kind 0 = fp32 lerp, 4 / 8 = copy of 4- / 8-byte integers (num_batches_tracked).  A tensor occupies
+ * s2s_ema_multi_blocks(n) blocks (0 for an empty tensor, which then owns no block), total = their sum. */
+long s2s_ema_multi_blocks(long n);
+int s2s_ema_multi(const void* desc, int ntensors, long total, const float* weight, void* stream);
 long s2s_pack_conv3x3_fwd_elems(int Cout, int Cin);
 long s2s_pack_conv3x3_dgrad_elems(int Cout, int Cin);
 int s2s_pack_conv3x3(int dtype, const float* w_oihw, void* w_fwd, void* w_dgrad, int Cout, int Cin, void* stream);

@@ -17,6 +17,7 @@ from .pix2pix import (Conv4x4Stride1, Conv4x4Stride2, ConvTranspose4x4Stride2, I
 from .pix2pix_engine import Pix2PixTrainer
 from .trainer import CFMTrainer
 from .optim import FusedAdam
+from .ema import FusedEMA
 from .multitask_trainer import MultiTaskTrainer
 from .evaluation import EvalAccumulator
 
@@ -25,5 +26,5 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "CFMTrainer", "ClassConditionalFlowUNet", "ClassConditionalFlowMatchingModule",
            "MaskConditionedFlowMatchingModule", "ROICharbonnierFlowMatchingModule", "ROIWeightedFlowMatchingModule",
            "checkpoint", "InstanceNormLeakyReLU", "Conv4x4Stride1", "Conv4x4Stride2", "ConvTranspose4x4Stride2",
-           "Pix2PixGenerator", "PatchGANDiscriminator", "Pix2PixTrainer", "FusedAdam", "MultiTaskTrainer",
+           "Pix2PixGenerator", "PatchGANDiscriminator", "Pix2PixTrainer", "FusedAdam", "FusedEMA", "MultiTaskTrainer",
            "EvalAccumulator"]

@@ -14,7 +14,11 @@ is keyed on the master weight's version counter.  This file is the file-level gl
                              conditional_flow_matching.py:93-94 ``compile: true``) and an optional prefix
   * ``load_weights``         into any of our modules, strict by default, with a readable report on mismatch
   * ``save_checkpoint``      Lightning-shaped dict: ``state_dict`` + ``optimizer_states`` (torch.optim.Adam layout,
-                             see CFMTrainer.optimizer_state_dict) + ``epoch`` / ``global_step``
+                             see CFMTrainer.optimizer_state_dict) + ``epoch`` / ``global_step``, and optionally
+                             ``ema_state_dict``: an EMA of the weights in torch.optim.swa_utils.AveragedModel's layout
+                             (``n_averaged`` + ``module.<keys>``: CFMTrainer.ema_state_dict, FusedEMA.state_dict).
+                             ``load_weights(net, ckpt["ema_state_dict"], strip_prefix="module.")`` puts the averaged
+                             weights into a bare network (keys outside the prefix, ``n_averaged``, are skipped)
 
 No reference-trained checkpoint exists offline, so the tests pin the format with a checkpoint
 written from the reference's own freshly initialised modules (tests/golden/make_golden.py).
@@ -60,11 +64,14 @@ def load_weights(module: torch.nn.Module, source, strip_prefix: Optional[str] = 
 
 
 def save_checkpoint(path: str, module: torch.nn.Module, optimizer_state: Optional[Dict] = None, epoch: int = 0,
-                    global_step: int = 0, extra: Optional[Dict] = None) -> Dict:
-    """Writes what the reference's loaders read (``state_dict``), plus the optimiser state in torch.optim layout."""
+                    global_step: int = 0, extra: Optional[Dict] = None, ema_state: Optional[Dict] = None) -> Dict:
+    """Writes what the reference's loaders read (``state_dict``), plus the optimiser state in torch.optim layout and,
+    when given, ``ema_state`` (AveragedModel layout) under ``ema_state_dict``."""
     ckpt = {"epoch": int(epoch), "global_step": int(global_step), "pytorch-lightning_version": LIGHTNING_VERSION_TAG,
             "state_dict": {k: v.detach().cpu().clone() for k, v in module.state_dict().items()},
             "optimizer_states": [optimizer_state] if optimizer_state is not None else [], "lr_schedulers": []}
+    if ema_state is not None:
+        ckpt["ema_state_dict"] = {k: v.detach().cpu().clone() for k, v in ema_state.items()}
     if extra:
         ckpt.update(extra)
     torch.save(ckpt, path)

@@ -3,6 +3,8 @@
 //   s2s_adam_step       torch.optim.Adam (coupled L2 weight decay, no amsgrad) over one flat fp32
 //                       parameter buffer -- the optimiser the reference builds in configure_optimizers
 //                       (src/models/conditional_flow_matching.py:112-131, configs/model/*.yaml:3-7).
+//   s2s_adam_ema_step   the same Adam with an exponential moving average of the weights in the same pass;
+//   s2s_ema_multi       that average over a list of tensors (BatchNorm buffers, the drop-in FusedEMA).
 //   s2s_pack_conv3x3    OIHW fp32 master weights -> the two MFMA operand layouts of conv3x3_mfma.hip:
 //                       forward  Wf[cin/32][tap][cout][32]  and data-gradient
 //                       Wd[cout/32][tap'][cin][32] = W[co][ci][2-kh'][2-kw'] (flipped, transposed); slabs in K-loop order.
@@ -80,6 +82,137 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamDesc* __restr
       m[i] = mi;
       v[i] = vi;
     }
+  }
+}
+
+// torch.lerp's two-branch form (aten/src/ATen/native/Lerp.h): exact at both ends, so weight 1.0 copies `b`.
+__device__ __forceinline__ float lerp_torch(float a, float b, float w) {
+  return fabsf(w) < 0.5f ? a + w * (b - a) : b - (b - a) * (1.f - w);
+}
+
+// Adam + EMA of the weights in one pass.  The parameter / moment arithmetic is adam_body's expression, statement for
+// statement (a run with the EMA on leaves p, m, v bit-equal to one without); the EMA lerps towards the new parameter
+// while it is still in a register.  16-byte accesses on all five streams (36 B per element: read p g m v ema, write
+// p m v ema), a grid-stride loop over a grid capped at the chip's residency (ema_grid), the < 4-element tail in block 0.
+__device__ __forceinline__ void adam_ema_elem(float& p, float g, float& m, float& v, float& e, float step_size,
+                                              float beta1, float beta2, float eps, float weight_decay, float bc2_sqrt,
+                                              float grad_scale, float w) {
+  // Rounding pinned to what adam_body compiles to (its gfx950 ISA): every multiply and add rounded on its own except
+  // the two fused ones written as fmaf -- left to contraction, this vectorised body fuses differently and m drifts by
+  // an ulp from the plain kernel's.
+#pragma clang fp contract(off)
+  const float pi = p;
+  float gi = g * grad_scale;
+  if (weight_decay != 0.f) gi = fmaf(weight_decay, pi, gi);
+  const float mi = m + (gi - m) * (1.f - beta1);
+  const float vi = v * beta2 + (1.f - beta2) * gi * gi;
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  const float pn = fmaf(-step_size, mi / denom, pi);     // adam_body: pi - step_size * (mi / denom), contracted
+  p = pn;
+  m = mi;
+  v = vi;
+  e = lerp_torch(e, pn, w);
+}
+
+__device__ __forceinline__ void adam_ema_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                              float* __restrict__ v, float* __restrict__ ema, long n, float lr,
+                                              float beta1, float beta2, float eps, float weight_decay, float bc1,
+                                              float bc2_sqrt, float grad_scale, float w) {
+  const float step_size = lr / bc1;
+  const long n4 = n >> 2;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    f32x4 pv = reinterpret_cast<const f32x4*>(p)[i];
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+    f32x4 mv = reinterpret_cast<const f32x4*>(m)[i];
+    f32x4 vv = reinterpret_cast<const f32x4*>(v)[i];
+    f32x4 ev = reinterpret_cast<const f32x4*>(ema)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float pk = pv[k], mk = mv[k], vk = vv[k], ek = ev[k];
+      adam_ema_elem(pk, gv[k], mk, vk, ek, step_size, beta1, beta2, eps, weight_decay, bc2_sqrt, grad_scale, w);
+      pv[k] = pk;
+      mv[k] = mk;
+      vv[k] = vk;
+      ev[k] = ek;
+    }
+    reinterpret_cast<f32x4*>(p)[i] = pv;
+    reinterpret_cast<f32x4*>(m)[i] = mv;
+    reinterpret_cast<f32x4*>(v)[i] = vv;
+    reinterpret_cast<f32x4*>(ema)[i] = ev;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const long i = (n4 << 2) + threadIdx.x;
+    float pk = p[i], mk = m[i], vk = v[i], ek = ema[i];
+    adam_ema_elem(pk, g[i], mk, vk, ek, step_size, beta1, beta2, eps, weight_decay, bc2_sqrt, grad_scale, w);
+    p[i] = pk;
+    m[i] = mk;
+    v[i] = vk;
+    ema[i] = ek;
+  }
+}
+
+__global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v,
+                                                       float* __restrict__ ema, long n, float lr, float beta1,
+                                                       float beta2, float eps, float weight_decay, float bc1,
+                                                       float bc2_sqrt, float grad_scale, float w) {
+  adam_ema_body(p, g, m, v, ema, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, grad_scale, w);
+}
+
+// hyper[8] as adam_dev_kernel; the EMA weight in device memory too (a captured step replays this launch unchanged)
+__global__ __launch_bounds__(256) void adam_ema_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ m, float* __restrict__ v,
+                                                           float* __restrict__ ema, long n,
+                                                           const float* __restrict__ hyper,
+                                                           const float* __restrict__ weight) {
+  adam_ema_body(p, g, m, v, ema, n, hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], hyper[5], hyper[6], hyper[7],
+                weight[0]);
+}
+
+// dst = lerp(dst, src, *weight) over a descriptor table (integer tensors copied): desc[t] = {dst, src, n, first block,
+// kind}; a block owns 4096 consecutive elements of one tensor, an empty tensor owns none (its first block is its
+// successor's, and the search below takes the LAST tensor starting at or before the block).  Plain loads and stores,
+// no atomics: every element is written by exactly one thread, whatever the grid.
+struct EmaDesc {
+  long dst, src, n, start, kind;
+};
+constexpr int EMA_MULTI_CHUNK = 4096;
+
+__global__ __launch_bounds__(256) void ema_multi_kernel(const EmaDesc* __restrict__ desc, int nt,
+                                                        const float* __restrict__ weight) {
+  int lo = 0, hi = nt - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (desc[mid].start <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  const EmaDesc d = desc[lo];
+  const long base = ((long)blockIdx.x - d.start) * EMA_MULTI_CHUNK;
+  const long end = d.n < base + EMA_MULTI_CHUNK ? d.n : base + EMA_MULTI_CHUNK;
+  if (d.kind == 0) {
+    float* __restrict__ dst = reinterpret_cast<float*>(d.dst);
+    const float* __restrict__ src = reinterpret_cast<const float*>(d.src);
+    const float w = weight[0];
+    long tail = base;
+    if (((d.dst | d.src) & 15) == 0) {          // base is a multiple of 4096 elements: aligned tensors stay aligned
+      const long nv = (end - base) >> 2;
+      for (long k = threadIdx.x; k < nv; k += 256) {
+        f32x4 a = *reinterpret_cast<const f32x4*>(dst + base + 4 * k);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(src + base + 4 * k);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a[j] = lerp_torch(a[j], b[j], w);
+        *reinterpret_cast<f32x4*>(dst + base + 4 * k) = a;
+      }
+      tail = base + (nv << 2);
+    }
+    for (long i = tail + threadIdx.x; i < end; i += 256) dst[i] = lerp_torch(dst[i], src[i], w);
+  } else if (d.kind == 8) {
+    long* __restrict__ dst = reinterpret_cast<long*>(d.dst);
+    const long* __restrict__ src = reinterpret_cast<const long*>(d.src);
+    for (long i = base + threadIdx.x; i < end; i += 256) dst[i] = src[i];
+  } else if (d.kind == 4) {
+    int* __restrict__ dst = reinterpret_cast<int*>(d.dst);
+    const int* __restrict__ src = reinterpret_cast<const int*>(d.src);
+    for (long i = base + threadIdx.x; i < end; i += 256) dst[i] = src[i];
   }
 }
 
@@ -243,6 +376,56 @@ extern "C" int s2s_adam_step_dev(float* p, const float* g, float* m, float* v, l
   if (!p || !g || !m || !v || !hyper) return S2S_ERR_NULL;
   if (n <= 0) return S2S_ERR_SHAPE;
   hipLaunchKernelGGL(adam_dev_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper);
+  S2S_LAUNCH_CHECK();
+  return S2S_OK;
+}
+
+// HBM streaming: enough 256-thread blocks for every float4, at most 2048 (256 CUs x 8 resident), grid-stride beyond
+inline int ema_grid(long n4) {
+  long b = (n4 + 255) / 256;
+  if (b > 2048) b = 2048;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+inline bool aligned16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
+
+extern "C" int s2s_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, long n, int step, float lr,
+                                 float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                 float ema_weight, void* stream) {
+  if (!p || !g || !m || !v || !ema) return S2S_ERR_NULL;
+  if (n <= 0 || step <= 0) return S2S_ERR_SHAPE;
+  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) || !aligned16(ema)) return S2S_ERR_ALIGN;
+  // the bias corrections exactly as s2s_adam_step forms them
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  hipLaunchKernelGGL(adam_ema_kernel, dim3(ema_grid(n >> 2)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr,
+                     beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale, ema_weight);
+  S2S_LAUNCH_CHECK();
+  return S2S_OK;
+}
+
+extern "C" int s2s_adam_ema_step_dev(float* p, const float* g, float* m, float* v, float* ema, long n,
+                                     const float* hyper, const float* ema_weight, void* stream) {
+  if (!p || !g || !m || !v || !ema || !hyper || !ema_weight) return S2S_ERR_NULL;
+  if (n <= 0) return S2S_ERR_SHAPE;
+  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) || !aligned16(ema)) return S2S_ERR_ALIGN;
+  hipLaunchKernelGGL(adam_ema_dev_kernel, dim3(ema_grid(n >> 2)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n,
+                     hyper, ema_weight);
+  S2S_LAUNCH_CHECK();
+  return S2S_OK;
+}
+
+// blocks one tensor of n elements occupies in s2s_ema_multi: none for an empty tensor (it must not shift the block map)
+extern "C" long s2s_ema_multi_blocks(long n) { return n < 0 ? S2S_ERR_SHAPE : (n + EMA_MULTI_CHUNK - 1) / EMA_MULTI_CHUNK; }
+
+// desc: device long[ntensors][5] = {dst, src, n, first block, kind}; total = all blocks (0: nothing to do)
+extern "C" int s2s_ema_multi(const void* desc, int ntensors, long total, const float* weight, void* stream) {
+  if (!desc || !weight) return S2S_ERR_NULL;
+  if (ntensors <= 0 || total < 0 || total >= (1L << 31)) return S2S_ERR_SHAPE;
+  if (total == 0) return S2S_OK;
+  hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream,
+                     static_cast<const EmaDesc*>(desc), ntensors, weight);
   S2S_LAUNCH_CHECK();
   return S2S_OK;
 }

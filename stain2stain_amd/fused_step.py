@@ -3,7 +3,7 @@ pix2pix_engine.Pix2PixTrainer):
 
   * ``FlatParams``     parameters of a network as views of one flat fp32 buffer, with flat gradient / Adam-moment
                        buffers in backward-completion order (gradient buckets are contiguous slices), the bucketer and
-                       the fused Adam over it
+                       the fused Adam over it; optionally a flat EMA of the parameters, updated inside that Adam pass
   * ``CapturedStep``   an optimisation step replayed as ONE captured hipGraph: eager warm-up, capture, static inputs,
                        the Adam scalars in device memory
 """
@@ -56,16 +56,43 @@ class FlatParams:
                                      "reduce_scatter" if sharded else "allreduce")
         self.step_count = 0
         broadcast_from_rank0([self.p], process_group)
+        self.ema: Optional[torch.Tensor] = None        # enable_ema()
+        self.ema_decay, self.n_averaged, self.ema_w = None, 0, None
+
+    def enable_ema(self, decay: float) -> None:
+        """Keep an exponential moving average of the parameters in ``ema`` (same slots as ``p``): every ``adam`` then
+        runs the fused Adam + EMA kernel, ``ema = lerp(ema, p_new, w)`` with w = 1 on the first update (a copy) and
+        ``1 - decay`` after -- torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn(decay), updated after
+        every optimiser step.  With a sharded optimiser each rank averages its own shards only (``gather_ema``)."""
+        self.ema_decay = ops.check_ema_decay(decay)
+        self.ema = self.p.clone()
+        self.n_averaged = 0
+        self.ema_w = ops.EmaWeightSlot(self.p.device)
+
+    def ema_weight(self) -> float:
+        return ops.ema_weight(self.n_averaged, self.ema_decay)
+
+    def gather_ema(self) -> None:
+        """Sharded optimiser: every rank's EMA shards to every rank (a COLLECTIVE in that mode, like ``state_dict``);
+        otherwise nothing to do."""
+        if self.ema is not None and self.n_averaged > 0:
+            self.bucketer.all_gather(self.ema)
 
     def adam(self, lr: float, betas: Tuple[float, float], eps: float, weight_decay: float,
              hyper_dev: Optional[torch.Tensor] = None) -> None:
         """``hyper_dev``: the Adam scalars in device memory (a captured step; the caller advances ``step_count`` and
         refreshes them before each replay) instead of kernel arguments."""
         self.bucketer.wait_all()
+        w = None
         if hyper_dev is None:
             self.step_count += 1
+            if self.ema is not None:        # (the weight goes to device memory too: the trainers' BatchNorm-buffer EMA)
+                w = self.ema_weight()
+                self.ema_w.push(w)
         for lo, hi in self.bucketer.shards():              # everything, or this rank's slices in sharded mode
-            self._adam_slice(lo, hi, lr, betas, eps, weight_decay, hyper_dev)
+            self._adam_slice(lo, hi, lr, betas, eps, weight_decay, hyper_dev, w)
+        if w is not None:
+            self.n_averaged += 1
         self.bucketer.all_gather(self.p)
 
     def adam_group(self, group: int, lr: float, betas: Tuple[float, float], eps: float, weight_decay: float,
@@ -73,11 +100,19 @@ class FlatParams:
         """Adam on the slice of parameter group ``group`` alone (the step counter is the caller's: ``begin_step``), for
         the update-in-backward of a trainer without a gradient exchange.  Adam is element-wise: the slices of all groups
         together are exactly ``adam``."""
+        if self.ema is not None:
+            raise NotImplementedError("stain2stain_amd: the per-group Adam (update in backward) has no EMA")
         self._adam_slice(*self.group_range[group], lr, betas, eps, weight_decay, hyper_dev)
 
-    def _adam_slice(self, lo: int, hi: int, lr, betas, eps, weight_decay, hyper_dev) -> None:
+    def _adam_slice(self, lo: int, hi: int, lr, betas, eps, weight_decay, hyper_dev, ema_w: Optional[float] = None) -> None:
         p, g, m, v = self.p[lo:hi], self.g[lo:hi], self.m[lo:hi], self.v[lo:hi]
-        if hyper_dev is None:
+        if self.ema is not None:
+            if hyper_dev is None:
+                ops.adam_ema_step_(p, g, m, v, self.ema[lo:hi], self.step_count, lr, betas[0], betas[1], eps, weight_decay,
+                                   self.bucketer.grad_scale, ema_w)
+            else:
+                ops.adam_ema_step_dev_(p, g, m, v, self.ema[lo:hi], hyper_dev, self.ema_w.dev)
+        elif hyper_dev is None:
             ops.adam_step_(p, g, m, v, self.step_count, lr, betas[0], betas[1], eps, weight_decay, self.bucketer.grad_scale)
         else:
             ops.adam_step_dev_(p, g, m, v, hyper_dev)
@@ -140,6 +175,7 @@ class CapturedStep:
             warnings.warn("stain2stain_amd: graph=True with a gradient exchange captures the RCCL collectives; this has "
                           "only been exercised at world size 1 (S2S_FORCE_DDP) -- treat it as experimental", stacklevel=3)
         counts = [fp.step_count for fp in flat_params]
+        averaged = [fp.n_averaged for fp in flat_params]
         if len(set(counts)) != 1:
             raise RuntimeError("graph=True: the optimisers must have taken the same number of steps")
         if self.hyper is None:
@@ -150,8 +186,8 @@ class CapturedStep:
                 try:
                     return body(*inputs, None)
                 except BaseException:
-                    for fp, n in zip(flat_params, counts):
-                        fp.step_count = n
+                    for fp, n, a in zip(flat_params, counts, averaged):
+                        fp.step_count, fp.n_averaged = n, a
                     raise
             static = [torch.empty_like(x, dtype=torch.float32).contiguous() for x in inputs]
             graph = torch.cuda.CUDAGraph()
@@ -163,7 +199,12 @@ class CapturedStep:
             s.copy_(x)
         lr, betas, eps, wd = hyper
         self.hyper.push(ops.adam_hyper(counts[0] + 1, lr, betas[0], betas[1], eps, wd, bk.grad_scale))
+        for fp in flat_params:
+            if fp.ema is not None:          # the EMA weight of this update, read by the captured kernels
+                fp.ema_w.push(fp.ema_weight())
         self.graph.replay()
         for fp in flat_params:
             fp.step_count += 1
+            if fp.ema is not None:
+                fp.n_averaged += 1
         return self.out.clone()

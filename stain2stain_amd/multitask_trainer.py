@@ -24,6 +24,7 @@ import torch.distributed as dist
 from . import engine, evaluation, ops
 from .components import FlowMatchingDecoder, SegmentationDecoder, SharedEncoder
 from .ddp import all_reduce_mean_scalar
+from .ema import TrainerEMA
 from .fused_step import FlatParams
 
 
@@ -59,14 +60,19 @@ class MultiTaskTrainer:
     become views of this trainer's flat buffers; ``state_dict`` / ``load_state_dict`` of the modules keep working).
 
     ``num_classes`` None: binary mask head, Dice + BCE; an integer: softmax Dice + CrossEntropy on class-index masks
-    (conditional_flow_matching_multitask_multiclassloss.py:92-159), ``ignore_index`` as there."""
+    (conditional_flow_matching_multitask_multiclassloss.py:92-159), ``ignore_index`` as there.
+
+    ``ema_decay``: an exponential moving average of the weights of all three networks, as CFMTrainer's (``ema_model()``
+    returns the averaged (encoder, flow_decoder, seg_decoder); the state layout is AveragedModel's over
+    ``torch.nn.ModuleDict(encoder=..., flow_decoder=..., seg_decoder=...)``)."""
 
     def __init__(self, encoder: SharedEncoder, flow_decoder: FlowMatchingDecoder, seg_decoder: SegmentationDecoder,
                  time_emb_dim: int = 256, lr: float = 1e-4, weight_decay: float = 1e-5,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, seg_loss_weight: float = 1.0,
                  dice_weight: float = 0.5, dice_smooth: float = 1.0, num_classes: Optional[int] = None,
                  ignore_index: int = -100, sigma: float = 0.0, bucket_mb: float = 4.0, process_group=None,
-                 sync_loss: bool = True, max_bucket_mb: float = 16.0, sharded_optimizer: bool = False):
+                 sync_loss: bool = True, max_bucket_mb: float = 16.0, sharded_optimizer: bool = False,
+                 ema_decay: Optional[float] = None, ema_buffers: bool = True):
         dev = next(encoder.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("stain2stain_amd: MultiTaskTrainer needs the networks on a GPU (HIP-only implementation)")
@@ -99,6 +105,10 @@ class MultiTaskTrainer:
         self.overlap_wgrad = True
         self._group = 0
         self._eval_owner = object()         # evaluate()'s workspaces, released by close()
+        self._ema = None
+        if ema_decay is not None:
+            self.fp.enable_ema(ema_decay)
+            self._ema = TrainerEMA(self.fp, [encoder, flow_decoder, seg_decoder], ema_buffers)
 
     @property
     def step_count(self) -> int:
@@ -163,8 +173,37 @@ class MultiTaskTrainer:
     def optimizer_step(self) -> None:
         engine.join_side(self._side)
         self.fp.adam(self.lr, self.betas, self.eps, self.wd)
+        if self._ema is not None:
+            self._ema.update_buffers()
         self.packer.repack()
         engine.mutation_epoch[0] += 1
+        if self._ema is not None:
+            self._ema.after_step()
+
+    # ------------------------------------------------------------------------------------------
+    # exponential moving average of the weights (ema_decay=)
+    def _ema_on(self) -> TrainerEMA:
+        if self._ema is None:
+            raise RuntimeError("stain2stain_amd: this trainer keeps no EMA (construct it with ema_decay=...)")
+        return self._ema
+
+    def ema_model(self) -> Tuple[SharedEncoder, FlowMatchingDecoder, SegmentationDecoder]:
+        """The averaged (encoder, flow_decoder, seg_decoder): persistent eval-mode copies whose parameters are views of
+        the flat EMA buffer (see CFMTrainer.ema_model).  A collective with ``sharded_optimizer``."""
+        return tuple(self._ema_on().modules())
+
+    def _ema_container(self) -> torch.nn.ModuleDict:
+        enc, fdec, sdec = self._ema_on().copies
+        return torch.nn.ModuleDict(dict(encoder=enc, flow_decoder=fdec, seg_decoder=sdec))
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """AveragedModel's layout over ModuleDict(encoder, flow_decoder, seg_decoder): ``n_averaged`` + ``module.*``."""
+        ema = self._ema_on()
+        ema.modules()
+        return ema.state_dict(self._ema_container().state_dict())
+
+    def load_ema_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        self._ema_on().load_state_dict(sd, self._ema_container())
 
     def step(self, source: torch.Tensor, target: torch.Tensor, mask: torch.Tensor,
              t: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -179,13 +218,15 @@ class MultiTaskTrainer:
         return total
 
     def evaluate(self, source: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, t: Optional[torch.Tensor] = None,
-                 accumulator: Optional[evaluation.EvalAccumulator] = None) -> Dict[str, torch.Tensor]:
+                 accumulator: Optional[evaluation.EvalAccumulator] = None,
+                 use_ema: bool = False) -> Dict[str, torch.Tensor]:
         """The validation / test values of one batch as device scalars: {"loss", "flow_loss", "seg_loss", "seg_dice",
         "seg_bce" | "seg_ce", "dice_coef", "iou"} (the reference's logging suffixes; dice_coef / iou as its test_step
         computes them, per-class means in the multiclass form).  Path sample, eval-mode forward of both heads
         (BatchNorm from the running statistics), forward-only head + MSE, one-pass segmentation loss + metrics.  Touches
         no training state, never waits for the device, runs no collective (``accumulator.compute()`` does, once) and
-        uses workspaces of its own.  ``accumulator``: the batch is added to it with weight ``source.shape[0]``."""
+        uses workspaces of its own.  ``accumulator``: the batch is added to it with weight ``source.shape[0]``.
+        ``use_ema``: score the averaged networks (``ema_model()``; a collective with ``sharded_optimizer``)."""
         with ops.workspace_owner(self._eval_owner), evaluation.eval_grad_mode():
             x0, x1 = source.float().contiguous(), target.float().contiguous()
             if t is None:
@@ -193,7 +234,7 @@ class MultiTaskTrainer:
             t = t.float().contiguous()
             eps_noise = torch.randn_like(x0) if self.sigma != 0.0 else None
             xt, ut = ops.cfm_sample(x0, x1, t, self.sigma, eps_noise)
-            enc, fdec, sdec = self.encoder, self.flow_decoder, self.seg_decoder
+            enc, fdec, sdec = self.ema_model() if use_ema else (self.encoder, self.flow_decoder, self.seg_decoder)
             flow = evaluation.flow_loss(enc, fdec, self.time_emb_dim, xt, t, ut)
             logits = evaluation.mask_logits(enc, sdec, x0)
             d = evaluation.segmentation_values(logits, mask, self.num_classes, self.ignore_index, self.dice_smooth,

@@ -943,10 +943,11 @@ class AdamHyperRing:
     that read it has completed -- the host runs ahead of the GPU by a step or two, never by the ring's length without
     this check stalling it)."""
     SLOTS = 16
+    WIDTH = 8
 
     def __init__(self, device):
-        self.dev = torch.zeros(8, dtype=torch.float32, device=device)
-        self._host = torch.empty((self.SLOTS, 8), dtype=torch.float32).pin_memory()
+        self.dev = torch.zeros(self.WIDTH, dtype=torch.float32, device=device)
+        self._host = torch.empty((self.SLOTS, self.WIDTH), dtype=torch.float32).pin_memory()
         self._done = [None] * self.SLOTS
         self._i = 0
 
@@ -968,6 +969,116 @@ def adam_step_dev_(p, g, m, v, hyper: torch.Tensor) -> None:
         raise RuntimeError("stain2stain_amd: adam hyper-parameter buffer must hold 8 floats")
     _native.check(_L().s2s_adam_step_dev(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), _f32(hyper), _stream()),
                   "adam_step_dev")
+
+
+# ---- exponential moving average of the weights (torch.optim.swa_utils.AveragedModel + get_ema_multi_avg_fn) ----
+class EmaWeightSlot(AdamHyperRing):
+    """The EMA's lerp weight (1.0 for the first update, ``1 - decay`` after) in device memory: ``dev`` is the float the
+    EMA kernels read, ``push(w)`` refreshes it in stream order without a host synchronisation, exactly as
+    ``AdamHyperRing`` refreshes the Adam scalars of a captured step (which therefore replays unchanged when the decay
+    changes or an EMA state is loaded).  The weight is 1.0 once and ``1 - decay`` after, so a push that would write the
+    value already there is skipped: a step then issues no copy for it."""
+    WIDTH = 1
+
+    def __init__(self, device):
+        super().__init__(device)
+        self._last = None
+
+    def push(self, w: float) -> None:
+        w = float(w)
+        if w != self._last:
+            super().push([w])
+            self._last = w
+
+
+def check_ema_decay(decay: float) -> float:
+    """torch.optim.swa_utils.get_ema_multi_avg_fn's check: ``decay`` in [0, 1]."""
+    decay = float(decay)
+    if not 0.0 <= decay <= 1.0:
+        raise ValueError(f"Invalid decay value {decay} provided. Please provide a value in [0,1] range.")
+    return decay
+
+
+def ema_weight(n_averaged: int, decay: float) -> float:
+    """The lerp weight of update number ``n_averaged + 1``: 1.0 copies (AveragedModel's first update), then 1 - decay
+    (the weight torch._foreach_lerp_ receives from get_ema_multi_avg_fn)."""
+    return 1.0 if n_averaged == 0 else 1.0 - decay
+
+
+def _f32_aligned(t: torch.Tensor) -> int:
+    ptr = _f32(t)
+    if ptr % 16:
+        raise RuntimeError("stain2stain_amd: the fused Adam + EMA wants 16-byte aligned buffers")
+    return ptr
+
+
+@_timed("adam_ema_step_")
+def adam_ema_step_(p, g, m, v, ema, step: int, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                   weight_decay: float = 0.0, grad_scale: float = 1.0, ema_weight: float = 1.0) -> None:
+    """``adam_step_`` (bit-equal p, m, v) + ``ema = lerp(ema, p_new, ema_weight)`` in the same pass."""
+    n = p.numel()
+    if not (g.numel() == m.numel() == v.numel() == ema.numel() == n):
+        raise RuntimeError("stain2stain_amd: adam_ema_step: p, g, m, v, ema must have the same number of elements")
+    _native.check(_L().s2s_adam_ema_step(_f32_aligned(p), _f32_aligned(g), _f32_aligned(m), _f32_aligned(v),
+                                         _f32_aligned(ema), n, int(step), float(lr), float(beta1), float(beta2),
+                                         float(eps), float(weight_decay), float(grad_scale), float(ema_weight),
+                                         _stream()), "adam_ema_step")
+
+
+def adam_ema_step_dev_(p, g, m, v, ema, hyper: torch.Tensor, weight: torch.Tensor) -> None:
+    """``adam_ema_step_`` with the Adam scalars (``adam_hyper``) and the EMA weight in device memory."""
+    if hyper.numel() != 8 or weight.numel() != 1:
+        raise RuntimeError("stain2stain_amd: adam_ema_step_dev wants 8 Adam scalars and 1 EMA weight")
+    n = p.numel()
+    if not (g.numel() == m.numel() == v.numel() == ema.numel() == n):
+        raise RuntimeError("stain2stain_amd: adam_ema_step_dev: p, g, m, v, ema must have the same number of elements")
+    _native.check(_L().s2s_adam_ema_step_dev(_f32_aligned(p), _f32_aligned(g), _f32_aligned(m), _f32_aligned(v),
+                                             _f32_aligned(ema), n, _f32(hyper), _f32(weight), _stream()),
+                  "adam_ema_step_dev")
+
+
+_EMA_KIND = {torch.float32: 0, torch.int64: 8, torch.int32: 4}
+
+
+class EmaTable:
+    """The descriptor table of one ``ema_multi_`` launch: ``dst = lerp(dst, src, w)`` for every (dst, src) pair, integer
+    tensors copied, and fp32 pairs too where ``copy[i]`` is set (bit-exact: copied as 4-byte words).  Built once (rows
+    are raw pointers: the tensors must stay where they are; ``signature`` lets a cache check that)."""
+
+    def __init__(self, pairs, copy=None):
+        L = _L()
+        pairs = list(pairs)
+        copy = [False] * len(pairs) if copy is None else list(copy)
+        rows, start, dev = [], 0, None
+        for (dst, src), cp in zip(pairs, copy):
+            if not (dst.is_cuda and src.is_cuda):
+                raise RuntimeError("stain2stain_amd: EMA tensors must live on the GPU (there is no CPU path)")
+            if dst.dtype != src.dtype or dst.dtype not in _EMA_KIND or dst.numel() != src.numel():
+                raise RuntimeError(f"stain2stain_amd: EMA pair {tuple(dst.shape)} {dst.dtype} <- {tuple(src.shape)} "
+                                   f"{src.dtype}: same element count and dtype, fp32 / int32 / int64 only")
+            if not (dst.is_contiguous() and src.is_contiguous()):
+                raise RuntimeError("stain2stain_amd: EMA tensors must be contiguous")
+            dev = dst.device if dev is None else dev
+            kind = _EMA_KIND[dst.dtype] or (4 if cp else 0)
+            rows.append([dst.data_ptr(), src.data_ptr(), dst.numel(), start, kind])
+            start += L.s2s_ema_multi_blocks(dst.numel())
+        if not rows:
+            raise RuntimeError("stain2stain_amd: an EMA table needs at least one tensor")
+        self.signature = self.signature_of(pairs)
+        self.n, self.total = len(rows), start
+        self.desc = torch.tensor(rows, dtype=torch.int64).to(dev)
+
+    @staticmethod
+    def signature_of(pairs) -> tuple:
+        return tuple((d.data_ptr(), s.data_ptr(), d.numel(), d.dtype) for d, s in pairs)
+
+
+@_timed("ema_multi_")
+def ema_multi_(table: EmaTable, weight: torch.Tensor) -> None:
+    """One launch of s2s_ema_multi over ``table`` with the lerp weight read from the device float ``weight``."""
+    if weight.numel() != 1:
+        raise RuntimeError("stain2stain_amd: ema_multi wants one device float as its weight")
+    _native.check(_L().s2s_ema_multi(table.desc.data_ptr(), table.n, table.total, _f32(weight), _stream()), "ema_multi")
 
 
 @_timed("pack_conv3x3")

@@ -21,6 +21,7 @@ import torch.distributed as dist
 
 from . import engine, evaluation, ops
 from .components import FlowUNet
+from .ema import TrainerEMA
 from .ddp import all_reduce_mean_scalar, broadcast_from_rank0
 from .fused_step import CapturedStep, FlatParams
 
@@ -91,7 +92,8 @@ class CFMTrainer:
     def __init__(self, net: FlowUNet, lr: float = 1e-4, weight_decay: float = 1e-5,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, sigma: float = 0.0,
                  bucket_mb: float = 4.0, process_group=None, sync_loss: bool = True, max_bucket_mb: float = 16.0,
-                 sharded_optimizer: bool = False, sync_batchnorm: bool = False, graph: bool = False):
+                 sharded_optimizer: bool = False, sync_batchnorm: bool = False, graph: bool = False,
+                 ema_decay: Optional[float] = None, ema_buffers: bool = True):
         """``graph``: ``step()`` replays ONE captured hipGraph per optimisation step (sample -> forward -> loss -> backward
         -> [gradient exchange] -> Adam -> repack: ~210 kernel launches) instead of issuing them from Python
         (fused_step.CapturedStep: eager warm-up, capture, bit-equal replays).
@@ -99,7 +101,12 @@ class CFMTrainer:
         bucket and all-gather the updated parameters (ddp.GradBucketer, mode "reduce_scatter") instead of all-reduce +
         a full Adam pass on every rank.  Same results, same wire volume, 1/world of the optimiser's HBM traffic.
         ``sync_batchnorm``: BatchNorm statistics over the global batch (Lightning's ``sync_batchnorm: True``,
-        configs/trainer/ddp.yaml:9; the stain experiments leave it off): two 2C-float all-reduces per layer and step."""
+        configs/trainer/ddp.yaml:9; the stain experiments leave it off): two 2C-float all-reduces per layer and step.
+        ``ema_decay``: keep an exponential moving average of the weights (None: off), the numbers of
+        torch.optim.swa_utils.AveragedModel(net, multi_avg_fn=get_ema_multi_avg_fn(ema_decay), use_buffers=ema_buffers)
+        updated after every step (stain2stain_amd.ema).  The parameters' average is updated inside the fused Adam pass,
+        the BatchNorm buffers' by one more launch; both are part of a captured step.  ``ema_model()`` is the averaged
+        network.  With it off nothing of the step changes."""
         dev = next(net.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("stain2stain_amd: CFMTrainer needs the network on a GPU (HIP-only implementation)")
@@ -127,6 +134,10 @@ class CFMTrainer:
         self.overlap_wgrad = True       # bench.py clears it on the steps whose kernels it brackets with HIP events
         self.graph = graph
         self._graph_step = CapturedStep()
+        self._ema = None
+        if ema_decay is not None:
+            self.fp.enable_ema(ema_decay)
+            self._ema = TrainerEMA(self.fp, [net], ema_buffers)
         # evaluate()'s workspaces: never the ones a captured training step has baked into its graph (released by close())
         self._eval_owner = object()
 
@@ -194,13 +205,20 @@ class CFMTrainer:
 
     def optimizer_step(self) -> None:
         self._enqueue_optimizer(None)
+        self._after_step()
+
+    def _after_step(self) -> None:
         engine.mutation_epoch[0] += 1
+        if self._ema is not None:
+            self._ema.after_step()
 
     def _enqueue_optimizer(self, hyper_dev: Optional[torch.Tensor]) -> None:
         """Join the exchange, Adam, [parameter all-gather], repack.  ``hyper_dev``: the Adam scalars in device memory
         (captured step) instead of kernel arguments."""
         engine.join_side(self._side)        # the weight gradients
         self.fp.adam(self.lr, self.betas, self.eps, self.wd, hyper_dev)
+        if self._ema is not None:
+            self._ema.update_buffers()
         self._repack()
 
     def _repack(self) -> None:
@@ -262,7 +280,7 @@ class CFMTrainer:
                                             self._step_body, [self.fp], (self.lr, self.betas, self.eps, self.wd))
             else:
                 loss = self._step_body(x0, x1, t, None)
-            engine.mutation_epoch[0] += 1
+            self._after_step()
             return loss
 
     def _step_body(self, x0, x1, t, hyper_dev) -> torch.Tensor:
@@ -274,14 +292,38 @@ class CFMTrainer:
             loss = loss / dist.get_world_size(self.pg)
         return loss
 
+    # ------------------------------------------------------------------------------------------
+    # exponential moving average of the weights (ema_decay=)
+    def _ema_on(self) -> TrainerEMA:
+        if self._ema is None:
+            raise RuntimeError("stain2stain_amd: this trainer keeps no EMA (construct it with ema_decay=...)")
+        return self._ema
+
+    def ema_model(self) -> FlowUNet:
+        """The averaged network: a persistent eval-mode FlowUNet whose parameters are views of the flat EMA buffer and
+        whose buffers hold the averaged BatchNorm statistics.  The same object throughout; it follows every later step
+        (its packed operands, folded BatchNorm constants and any sampler graph are refreshed at first use after a step).
+        With ``sharded_optimizer`` a COLLECTIVE (the EMA shards are all-gathered)."""
+        return self._ema_on().modules()[0]
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """AveragedModel's layout: ``n_averaged`` + ``module.<FlowUNet keys>`` (loads into AveragedModel and back)."""
+        return self._ema_on().state_dict(self.ema_model().state_dict())
+
+    def load_ema_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        ema = self._ema_on()
+        ema.load_state_dict(sd, ema.copies[0])
+
     def evaluate(self, x0: torch.Tensor, x1: torch.Tensor, t: Optional[torch.Tensor] = None,
-                 accumulator: Optional[evaluation.EvalAccumulator] = None) -> Dict[str, torch.Tensor]:
+                 accumulator: Optional[evaluation.EvalAccumulator] = None,
+                 use_ema: bool = False) -> Dict[str, torch.Tensor]:
         """The validation loss of one batch, {"loss": device scalar} (conditional_flow_matching.py:88-97): path sample,
         eval-mode forward (BatchNorm from the running statistics), forward-only head + MSE.  Touches no training state
         (parameters, running statistics, gradients, Adam moments, step count, packed weights), never waits for the device,
         runs no collective (``accumulator.compute()`` does that once per epoch) and runs eagerly beside a captured step,
-        on workspaces of its own.  ``accumulator``: the batch is added to it with weight ``x0.shape[0]``."""
-        net = self.net
+        on workspaces of its own.  ``accumulator``: the batch is added to it with weight ``x0.shape[0]``.
+        ``use_ema``: score the averaged network (``ema_model()``; a collective with ``sharded_optimizer``)."""
+        net = self.ema_model() if use_ema else self.net
         with ops.workspace_owner(self._eval_owner), evaluation.eval_grad_mode():
             x0, x1 = x0.float().contiguous(), x1.float().contiguous()
             if t is None:
