@@ -1,6 +1,5 @@
-"""Build (under the package's build lock) and load the -DS2S_ABLATE library -- the superseded forward loops and the timing
-ablations whose results are wrong by construction (S2S_CONV_DBG bits 1-32, S2S_CONV_DMA) -- for the measurement scripts in
-this directory: ``import ablate_lib`` as the FIRST import of a script that wants them.  The product package never loads
+"""Build (under the package's build lock) and load the -DS2S_ABLATE library -- the timing ablations whose results are
+wrong by construction (S2S_CONV_DBG bits 1-32, 256, 512, 1024) -- for the measurement scripts in this directory: ``import ablate_lib`` as the FIRST import of a script that wants them.  The product package never loads
 this library; there is no environment variable that makes it."""
 import fcntl
 import os

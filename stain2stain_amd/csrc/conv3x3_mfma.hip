@@ -21,9 +21,9 @@
 //   * the input can come from two tensors (channels [0,c0) from x0, [c0,c0+c1) from x1): this is the
 //     decoder's torch.cat([skip, up], dim=1) (task_decoders.py:49) without materialising the cat.
 //
-// T = bf16: operands are staged as they are (throughput mode).
-// T = float ("split" mode): every fp32 operand is staged as three bf16 images h = bf16(x),
-//   m = bf16(x - h), l = bf16(x - h - m) (24 mantissa bits in total) and each product is formed on the
+// bf16 (throughput mode) runs on the LDS-DMA loops below (conv3x3_dma16_kernel and its persistent and staged forms).
+// The register-staged loop (conv3x3_mfma_kernel) is the fp32 ("split") mode: every fp32 operand is staged as three bf16
+//   images h = bf16(x), m = bf16(x - h), l = bf16(x - h - m) (24 mantissa bits in total) and each product is formed on the
 //   same MFMA path from the six partial products of order <= 2^-18 (hh, hm, mh, hl, lh, mm), smallest
 //   first, fp32 accumulation: fp32-grade products at 6/16 of the cost of the f32 MFMA.  This is the
 //   parity mode that is checked against the fp32 oracle.
@@ -32,15 +32,15 @@
 #include <type_traits>
 #include <utility>
 
-// Timing ablations that change results (skip a DMA, the MFMAs, the stores ...) and the superseded forward loops are
-// compiled only with -DS2S_ABLATE (stain2stain_amd/_native.py build(ablate=True) -> libstain2stain_hip_ablate.so, used by
-// scripts/ alone); the product library cannot be switched into them by an environment variable.
+// Timing ablations that change results (skip a DMA, the MFMAs, the stores ...) are compiled only with -DS2S_ABLATE
+// (stain2stain_amd/_native.py build(ablate=True) -> libstain2stain_hip_ablate.so, used by scripts/ alone); the product
+// library cannot be switched into them by an environment variable.
 #ifdef S2S_ABLATE
 #define S2S_ABL(cond) (cond)
 #define S2S_DBG_MASK (~0)
 #else
 #define S2S_ABL(cond) false
-#define S2S_DBG_MASK (64 | 128)
+#define S2S_DBG_MASK 64
 #endif
 
 struct Conv3x3Args {
@@ -76,18 +76,11 @@ struct Conv3x3Args {
   // every XCD has its own L2, so the grid is cut into xsp x xsn = 8 blocks (pixel-tile ranges x output-channel-tile
   // ranges), one per XCD, walked output-channel tile fastest; xsp = 0 = the plain order.
   int xsp, xsn;
-  long stat_rows;  // rows per channel of stat_part (tiles, or tiles x wave rows with the register epilogue)
-  int direct_ep;   // 1: launches without statistics store straight from the accumulators (conv_epilogue16_direct); S2S_CONV_EPI=lds: 0
-  int stat_carry;  // persistent kernel with one channel tile: a wave row's statistics are carried over its tiles and
-                   // written once, row = workgroup * WM + wave row (stat_rows = workgroups * WM)
-  long stat_rows_req;   // rows the caller sized stat_part for (0: tiles * WM / tiles, the per-tile forms)
-  int dbg;   // S2S_CONV_DBG: 64 = clock probe, 128 = old LDS slot key; -DS2S_ABLATE builds only: bit0 = no weight DMA in the
-             // 32x32x16 loop, bit1 = no MFMA, bit2 = no halo DMA, 8 = no global stores, 16 = no epilogue
+  long stat_rows;  // rows per channel of stat_part (Conv3x3Plan::stat_rows)
+  long stat_rows_req;   // rows the caller sized stat_part for (0: the per-tile layout, s2s_conv3x3_stat_blocks)
+  int dbg;   // S2S_CONV_DBG: 64 = clock probe; -DS2S_ABLATE builds only: bit0 = no weight DMA, bit1 = no MFMA, bit2 = no
+             // halo DMA, 8 = no global stores, 16 = no epilogue
 };
-
-// launches without statistics store straight from the accumulators (conv_epilogue16_direct; the LDS-staged epilogue stays
-// for the launches that take BatchNorm partials through it)
-static int direct_ep_default() { return 1; }
 
 namespace {
 
@@ -105,17 +98,6 @@ constexpr int ROWB = 80;  // LDS bytes per 32-channel row (64 data + 16 pad)
 constexpr int STEM_HALO_BYTES = 3 * 18 * 18 * 4;   // fp32 halo of a 16x16 tile, up to 3 input channels
 
 template <typename T> struct Piece;
-template <> struct Piece<bf16_t> {
-  bf16x8 v;
-  __device__ __forceinline__ void zero() {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (bf16_t)0.0f;
-  }
-  __device__ __forceinline__ void load(const bf16_t* p) { v = *reinterpret_cast<const bf16x8*>(p); }
-  __device__ __forceinline__ void to_lds(char* hi, int /*img_stride*/, int off) const {
-    *reinterpret_cast<bf16x8*>(hi + off) = v;
-  }
-};
 template <> struct Piece<float> {
   f32x4 a, b;
   __device__ __forceinline__ void zero() {
@@ -459,7 +441,7 @@ __global__ __launch_bounds__(256, (std::is_same<T, float>::value ? 1 : 2)) void 
 }
 
 // =========================================================================================================
-// bf16 main loop v2: operands go global -> LDS by LDS-DMA (global_load_lds_dwordx4), no VGPR staging.
+// bf16 LDS-DMA main loops: operands go global -> LDS by LDS-DMA (global_load_lds_dwordx4), no VGPR staging.
 //   * LDS rows are 64 B (32 channels), unpadded because a DMA wave-instruction writes 1 KiB linearly
 //     (16 rows x 4 pieces); bank conflicts are removed by an XOR swizzle instead: piece p of row r is stored
 //     in slot p ^ ((r >> 2) & 3).  For the DMA this swizzle sits on the per-lane SOURCE address (lane l
@@ -484,182 +466,11 @@ __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-#ifdef S2S_ABLATE   // the 32x32x16 form of the LDS-DMA loop: ablation builds only (scripts/), never in the product library
-template <int TH, int TW, int BN, int WM, int WN, int NS>
-__global__ __launch_bounds__(256, 2) void conv3x3_dma_kernel(Conv3x3Args a) {
-  using T = bf16_t;
-  // halo image: row index = hy * HP + hx with the pitch HP = TW + 4 a multiple of 4, so that the bank-row phase
-  // (row & 3) equals hx & 3 and the swizzle can be keyed on hx alone: slot = piece ^ ((hx >> 2) & 3).  A tap's
-  // kh then is a constant byte offset (folded into the ds_read immediate) and only kw changes the swizzle.
-  constexpr int HP = TW + 4, HH_ = TH + 2, ROWS = HH_ * HP;
-  constexpr int NGA = (ROWS + 15) / 16, HG = (NGA + 3) / 4;   // halo row groups, DMA instr per wave
-  constexpr int A_BYTES = HG * 4 * 1024;
-  constexpr int BG = BN / 64;                                 // weight DMA instr per wave per slab
-  constexpr int B_BYTES = BN * 64;
-  constexpr int BM = TH * TW, WTM = BM / WM, WTN = BN / WN, MI = WTM / 32, NI = WTN / 32;
-  static_assert(WM * WN == 4 && BN % 64 == 0 && (NS == 3 || NS == 4), "configuration");
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* const ldsA = smem;                    // [2][A_BYTES]
-  char* const ldsB = smem + 2 * A_BYTES;      // [NS][B_BYTES]
-
-  const T* __restrict__ x0 = static_cast<const T*>(a.x0);
-  const T* __restrict__ x1 = static_cast<const T*>(a.x1);
-  const char* __restrict__ wp = static_cast<const char*>(a.w);
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WN, wn = wave % WN;
-  const int r = lane & 31, h = lane >> 5;
-
-  int bt = blockIdx.x;
-  const int tx = bt % a.tilesX; bt /= a.tilesX;
-  const int ty = bt % a.tilesY;
-  const int img = bt / a.tilesY;
-  const int y0 = ty * TH, x0p = tx * TW;
-  const int n0 = blockIdx.y * BN;
-  const int ctot = a.c0 + a.c1;
-
-  // ---- DMA lane geometry ----
-  const int drow = lane >> 2, dslot = lane & 3;
-  int apix[HG];    // NHWC pixel index of this lane's halo row in DMA group j, -1 = zero page
-  int apc[HG];     // channel offset (elements) inside a 32-channel chunk of the piece this lane fetches
-#pragma unroll
-  for (int j = 0; j < HG; ++j) {
-    const int row = (wave + 4 * j) * 16 + drow;
-    const int hy = row / HP, hx = row - hy * HP;
-    const int gy = y0 - 1 + hy, gx = x0p - 1 + hx;
-    apix[j] = (row < ROWS && hx < TW + 2 && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W)
-                  ? (img * a.H + gy) * a.W + gx : -1;
-    apc[j] = (dslot ^ ((hx >> 2) & 3)) * 8;
-  }
-  // weights: slab `it` = [Cout][32] at byte offset it * Cout * 64; every lane keeps a running pointer to its
-  // row piece (rows past Cout park on the zero page with a zero stride)
-  const char* wptr[BG];
-  int wstep[BG];
-#pragma unroll
-  for (int j = 0; j < BG; ++j) {
-    const int n = (wave + 4 * j) * 16 + drow;
-    const bool ok = n0 + n < a.Cout;
-    wptr[j] = ok ? wp + ((long)(n0 + n) * 32 + ((dslot ^ ((n >> 2) & 3)) * 8)) * 2 : g_zero_page;
-    wstep[j] = ok ? a.Cout * 64 : 0;
-  }
-
-  auto dma_halo = [&](int c) {
-    char* dst = ldsA + (c & 1) * A_BYTES + wave * 1024;
-#pragma unroll
-    for (int j = 0; j < HG; ++j) {
-      const int ch = c * 32 + apc[j];
-      const void* g = g_zero_page;
-      if (apix[j] >= 0) {
-        if (ch < a.c0) g = x0 + (long)apix[j] * a.ld0 + ch;
-        else if (ch < ctot) g = x1 + (long)apix[j] * a.ld1 + (ch - a.c0);
-      }
-      dma16(g, dst + j * 4096);
-    }
-  };
-  auto dma_w = [&](int slot) {   // next slab in sequence
-    char* dst = ldsB + slot * B_BYTES + wave * 1024;
-#pragma unroll
-    for (int j = 0; j < BG; ++j) {
-      dma16(wptr[j], dst + j * 4096);
-      wptr[j] += wstep[j];
-    }
-  };
-
-  // ---- fragment geometry (computed once) ----
-  int aofs[MI][3];   // byte offset of this lane's pixel row for tap (0, kw), k-step 0
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi) {
-    const int m = wm * WTM + mi * 32 + r;
-    const int py = m / TW, px = m - py * TW;
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw)
-      aofs[mi][kw] = (py * HP + px + kw) * 64 + ((h ^ (((px + kw) >> 2) & 3)) << 4);
-  }
-  int bofs[NI];
-#pragma unroll
-  for (int ni = 0; ni < NI; ++ni) {
-    const int n = wn * WTN + ni * 32 + r;
-    bofs[ni] = n * 64 + ((h ^ ((n >> 2) & 3)) << 4);
-  }
-
-  f32x16 acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[mi][ni][j] = 0.f;
-
-  // one tap: MFMAs of tap `tap` from halo buffer Ab and weight slot (it % NS)
-  auto compute = [&](auto tapc, const char* Ab, const char* Bb) {
-    constexpr int tap = decltype(tapc)::value;
-    constexpr int kh = tap / 3, kw = tap % 3;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[MI], bfr[NI];
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-        af[mi] = *reinterpret_cast<const bf16x8*>(Ab + (aofs[mi][kw] ^ (ks << 5)) + kh * HP * 64);
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) bfr[ni] = *reinterpret_cast<const bf16x8*>(Bb + (bofs[ni] ^ (ks << 5)));
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi], bfr[ni], acc[mi][ni], 0, 0, 0);
-    }
-  };
-
-  // ---- prologue: halo 0 and the first NS-1 slabs (slabs past the end are harmless: they read the next
-  //      chunk's bytes of the packed weights only if they exist, so clamp by count) ----
-  const int nit = a.nchunk * 9;
-  dma_halo(0);
-  static_for<NS - 1>([&](auto k) { dma_w(decltype(k)::value); });   // nit >= 9 > NS-1
-  wait_vm<0>();
-  __builtin_amdgcn_s_barrier();
-
-  // ---- steady state: every chunk but the last; no run-time conditions inside a tap ----
-  int c = 0;
-  for (; c + 1 < a.nchunk; ++c) {
-    const char* Ab = ldsA + (c & 1) * A_BYTES;
-    const int it0 = c * 9;
-    static_for<9>([&](auto tapc) {
-      constexpr int tap = decltype(tapc)::value;
-      if (tap == 0) { if (!(a.dbg & 4)) dma_halo(c + 1); else { static_for<HG>([&](auto) { dma16(g_zero_page, ldsA + ((c + 1) & 1) * A_BYTES + wave * 1024); }); } }
-      if (!(a.dbg & 1)) dma_w((it0 + tap + NS - 1) % NS);            // the slot read one tap ago
-      else { static_for<BG>([&](auto) { dma16(g_zero_page, ldsB + wave * 1024); }); }
-      if (!(a.dbg & 2)) compute(tapc, Ab, ldsB + ((it0 + tap) % NS) * B_BYTES);
-      __builtin_amdgcn_sched_barrier(0);           // this tap's MFMAs (and LDS reads) stay ahead of the barrier
-      // retire slab it+1: the (NS-2) younger slabs, and the halo while it is younger, may stay in flight
-      wait_vm<(NS - 2) * BG + (tap <= NS - 3 ? HG : 0)>();
-      __builtin_amdgcn_s_barrier();
-    });
-  }
-  // ---- last chunk: no further halo; slabs run out NS-1 taps before the end ----
-  {
-    const char* Ab = ldsA + (c & 1) * A_BYTES;
-    const int it0 = c * 9;
-    static_for<9>([&](auto tapc) {
-      constexpr int tap = decltype(tapc)::value;
-      if (tap + NS - 1 < 9) dma_w((it0 + tap + NS - 1) % NS);
-      compute(tapc, Ab, ldsB + ((it0 + tap) % NS) * B_BYTES);
-      __builtin_amdgcn_sched_barrier(0);
-      if (tap + NS - 1 < 9) wait_vm<(NS - 2) * BG>(); else wait_vm<0>();
-      __builtin_amdgcn_s_barrier();
-    });
-  }
-  conv_epilogue<T, TH, TW, BN, WM, WN, 2 * A_BYTES + NS * B_BYTES>(a, acc, smem, img, y0, x0p, n0);
-}
-
-#endif  // S2S_ABLATE
-
 // =========================================================================================================
-// bf16 main loop v3: the LDS-DMA loop above on v_mfma_f32_16x16x32_bf16.  One MFMA covers the whole 32-channel
+// bf16 main loop v3: the LDS-DMA loop on v_mfma_f32_16x16x32_bf16.  One MFMA covers the whole 32-channel
 // chunk of a tap (K = 32), a lane's A/B fragment is one 16-B piece (row = lane & 15, piece = lane >> 4), and the
-// result tile has col = lane & 15, rows 4*(lane >> 4) + reg.  Same FLOP per cycle as the 32x32x16 form, but the
-// chip holds a higher clock on it under load (MI355X_MICROARCH.md, DVFS give-back 7), which is what bounds the
+// result tile has col = lane & 15, rows 4*(lane >> 4) + reg.  Same FLOP per cycle as the 32x32x16 form it replaced, but
+// the chip holds a higher clock on it under load (MI355X_MICROARCH.md, DVFS give-back 7), which is what bounds the
 // conv stack on real data.  The swizzle uses slot = piece ^ ((-(row >> 2)) & 3): with the 16x16 lane->row map a
 // ds_read_b128 lane group takes rows {0-3, 12-15} of one piece and rows {4-11} of the next, and this key keeps
 // all sixteen 16-B slots of the bank row distinct (the plain (row >> 2) & 3 key gives a 2-way conflict here).
@@ -997,9 +808,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_dma16_kernel(Conv3x3Args a) {
   // {4-11} of the next: the key 2 * ((column >> 2) & 1) keeps the sixteen slots of every such group distinct for all
   // three shifts (exhaustive check over shifts, row blocks and lane groups); the earlier (-(column >> 2)) & 3 was only
   // conflict-free unshifted, and SQ_LDS_BANK_CONFLICT showed 29 % of this kernel's LDS cycles as conflicts
-  // (profiles/r02_f_sq_counters.json; S2S_CONV_DBG=128 selects the old key).
-  const bool old_key = (a.dbg & 128) != 0;
-  auto akey = [&](int col) { return old_key ? ((-(col >> 2)) & 3) : (((col >> 2) & 1) << 1); };
+  // (profiles/r02_f_sq_counters.json).
+  auto akey = [](int col) { return ((col >> 2) & 1) << 1; };
   int apix[HG], apc[HG];
 #pragma unroll
   for (int j = 0; j < HG; ++j) {
@@ -1160,12 +970,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_dma16_kernel(Conv3x3Args a) {
     return;
   }
   const OutMap om{1, 0, 0, a.H, a.W};
-  if (a.direct_ep) {      // registers -> global memory (conv_epilogue16_direct), statistics in registers too
-    if (a.stat_part) conv_epilogue16_direct<TH, TW, BN, WM, WN, false, true>(a, acc, biasr, img, y0, x0p, n0, tid, om, (long)tile_id * WM + wm);
-    else if (a.ep_scale) conv_epilogue16_direct<TH, TW, BN, WM, WN, true>(a, acc, biasr, img, y0, x0p, n0, tid, om);
-    else conv_epilogue16_direct<TH, TW, BN, WM, WN, false>(a, acc, biasr, img, y0, x0p, n0, tid, om);
-  } else if (a.ep_scale) conv_epilogue16<TH, TW, BN, WM, WN, 2 * A_BYTES + NS * B_BYTES, true>(a, acc, biasr, smem, img, y0, x0p, n0, tid, tile_id, om);
-  else conv_epilogue16<TH, TW, BN, WM, WN, 2 * A_BYTES + NS * B_BYTES, false>(a, acc, biasr, smem, img, y0, x0p, n0, tid, tile_id, om);
+  // registers -> global memory (conv_epilogue16_direct), statistics in registers too
+  if (a.stat_part) conv_epilogue16_direct<TH, TW, BN, WM, WN, false, true>(a, acc, biasr, img, y0, x0p, n0, tid, om, (long)tile_id * WM + wm);
+  else if (a.ep_scale) conv_epilogue16_direct<TH, TW, BN, WM, WN, true>(a, acc, biasr, img, y0, x0p, n0, tid, om);
+  else conv_epilogue16_direct<TH, TW, BN, WM, WN, false>(a, acc, biasr, img, y0, x0p, n0, tid, om);
   if ((a.dbg & 64) && threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 8192) { g_clk[blockIdx.x * 4 + 0] = c0_; g_clk[blockIdx.x * 4 + 1] = __builtin_readcyclecounter(); g_clk[blockIdx.x * 4 + 2] = w0_; g_clk[blockIdx.x * 4 + 3] = wall_clock64(); }
 }
 
@@ -1419,32 +1227,62 @@ __global__ __launch_bounds__(256, 2) void conv3x3_pers16_kernel(Conv3x3Args a, i
   if constexpr (STATS == 2) conv_stats_flush<BN, WN>(a, cs1, cs2, cur.n0, tid, (long)blockIdx.x * WM + wm);
 }
 
-// Grid and XCD cut of a persistent launch over GX pixel tiles x GY channel tiles (shared with s2s_conv3x3_stat_rows: with
-// one channel tile the statistics take grid * WM rows)
-struct PersPlan { int grid, xsp, xsn; };
-inline PersPlan pers_plan(const Conv3x3Args& a, int GX, int GY) {
-  PersPlan p{1, 0, 1};
-  const long ntiles = (long)GX * GY;
-  if (ntiles % 8 == 0) {
-    const double act = 2.0 * a.B * a.H * a.W * (a.c0 + a.c1), wb = 2.0 * 9 * (a.c0 + a.c1) * a.Cout;
-    double best = 0;
-    for (int sp = 8; sp >= 1; sp >>= 1) {
-      const int sn = 8 / sp;
-      if (GX % sp || GY % sn) continue;
-      const double cost = sn * act + sp * wb;
-      if (!p.xsp || cost < best) { best = cost; p.xsp = sp; p.xsn = sn; }
-    }
-  }
-  constexpr int slots = 512;                           // 2 per CU (swept in round 3: no better grid)
-  int grid = (int)(ntiles < slots ? ntiles : slots);
-  if (p.xsp && grid > 8) grid -= grid % 8;             // a stride that is a multiple of 8 keeps a workgroup inside its XCD's block
-  p.grid = grid < 1 ? 1 : grid;
-  return p;
+// ---- tile configuration table -----------------------------------------------------------------------
+// The largest tile whose grid still gives every CU about two workgroups wins; small feature maps
+// (16x16 ... 32x32 at batch 16) fall through to smaller tiles so that the 256 CUs stay busy.
+// wm: wave rows of the four waves (the per-tap kernels' WM; WN = 4 / wm): a per-tile statistics layout has one row per
+// (tile, wave row).  pers: the tile also runs on the persistent kernel (the 256-pixel x 128-channel tiles need 128
+// accumulator + 48 fragment registers: with the tile loop's state they spill, so they stay on the one-tile kernel).
+struct TileCfg { int th, tw, bn, wm; bool pers; };
+constexpr TileCfg kBf16Cfg[8] = {{8, 32, 128, 2, false}, {8, 32, 64, 4, true}, {4, 32, 128, 2, true}, {4, 32, 64, 2, true},
+                                 {16, 16, 128, 2, false}, {16, 16, 64, 4, true}, {8, 16, 128, 2, true}, {8, 16, 64, 2, true}};
+constexpr TileCfg kF32Cfg[2] = {{4, 32, 64, 2, false}, {8, 16, 64, 2, false}};
+constexpr int kMinBlocks = 448;
+
+inline long cfg_blocks(const TileCfg& c, int B, int H, int W, int Cout) {
+  return (long)B * cdiv(H, c.th) * cdiv(W, c.tw) * cdiv(Cout, c.bn);
 }
 
-template <int TH, int TW, int BN, int WM, int WN>
-int launch_pers16(Conv3x3Args& a, hipStream_t s) {
-  constexpr int NS = 4;
+int select_cfg(int dtype, int B, int H, int W, int Cout) {
+  if (dtype == S2S_F32) return W <= 16 ? 1 : 0;
+  const int first = W <= 16 ? 4 : 0;
+  int best = -1;
+  long best_blocks = -1;
+  for (int i = first; i < first + 4; ++i) {
+    const TileCfg& c = kBf16Cfg[i];
+    if (c.bn == 128 && (Cout <= 64 || (Cout % 128 != 0 && Cout % 128 <= 64 && Cout < 512))) continue;   // half-empty N tile
+    const long nb = cfg_blocks(c, B, H, W, Cout);
+    if (nb >= kMinBlocks) return i;
+    if (nb > best_blocks) { best_blocks = nb; best = i; }
+  }
+  return best;
+}
+
+// How a 3x3 launch runs, decided once from (dtype, Conv3x3Args) by conv3x3_plan(): dispatch() launches what it says, and
+// s2s_conv3x3_stat_blocks / _stat_rows / _staged / _ksplit report from it.
+enum Conv3x3Family {
+  kStageResident,   // conv3x3_stage_kernel, the whole filter resident in LDS
+  kStageStream,     // conv3x3_stage_kernel, the filter streamed
+  kPersCarry,       // conv3x3_pers16_kernel, statistics carried per (workgroup, wave row)
+  kPers,            // conv3x3_pers16_kernel, per-tile statistics or none
+  kTap,             // conv3x3_dma16_kernel, one tile per workgroup (split-K over gridDim.z)
+  kSplitF32,        // conv3x3_mfma_kernel<float>, the fp32 parity mode
+};
+struct Conv3x3Plan {
+  int rc;           // S2S_OK, or S2S_ERR_SHAPE: stat_rows_req matches no layout
+  int family;
+  int cfg;          // kBf16Cfg / kF32Cfg index (the staged kernel's tile is 16 x 32 x 64)
+  int gx, gy;       // pixel tiles x channel tiles of the family's tile
+  int grid;         // workgroups of the staged and persistent kernels (the others launch gx x gy x ksplit)
+  int xsp, xsn;     // XCD cut (Conv3x3Args)
+  int ksplit;
+  long stat_rows;   // rows per channel of stat_part
+};
+
+template <int ID>
+int launch_pers16(Conv3x3Args& a, const Conv3x3Plan& p, hipStream_t s) {
+  constexpr TileCfg c = kBf16Cfg[ID];
+  constexpr int TH = c.th, TW = c.tw, BN = c.bn, WM = c.wm, WN = 4 / WM, NS = 4;
   constexpr int ROWS = (TH + 2) * (TW + 4);
   constexpr int HG = ((ROWS + 15) / 16 + 3) / 4;
   constexpr int lds = 2 * HG * 4 * 1024 + NS * BN * 64;
@@ -1458,19 +1296,8 @@ int launch_pers16(Conv3x3Args& a, hipStream_t s) {
   if (int rc = s2s_allow_dyn_lds(reinterpret_cast<const void*>(kern_s), lds, &attr_s)) return rc;
   if (int rc = s2s_allow_dyn_lds(reinterpret_cast<const void*>(kern_c), lds, &attr_c)) return rc;
   if (int rc = s2s_allow_dyn_lds(reinterpret_cast<const void*>(kern_d), lds, &attr_d)) return rc;
-  const int GX = a.B * a.tilesY * a.tilesX, GY = cdiv(a.Cout, BN);
-  const long ntiles = (long)GX * GY;
-  const PersPlan pl = pers_plan(a, GX, GY);
-  a.xsp = pl.xsp; a.xsn = pl.xsn;
-  const int grid = pl.grid;
-  // statistics rows: one per (workgroup, wave row) when the caller sized the buffer for that (s2s_conv3x3_stat_rows) and
-  // there is a single channel tile; else one per (tile, wave row)
-  a.stat_carry = a.stat_part && GY == 1 && a.stat_rows_req == (long)grid * WM;
-  if (a.stat_part && !a.stat_carry && a.stat_rows_req && a.stat_rows_req != (long)GX * WM) return S2S_ERR_SHAPE;
-  a.stat_rows = a.stat_carry ? (long)grid * WM : (long)GX * WM;
-  if (a.stat_carry) hipLaunchKernelGGL(kern_c, dim3(grid), dim3(256), lds, s, a, (int)ntiles, GX, GY);
-  else if (a.stat_part) hipLaunchKernelGGL(kern_s, dim3(grid), dim3(256), lds, s, a, (int)ntiles, GX, GY);
-  else hipLaunchKernelGGL(kern_d, dim3(grid), dim3(256), lds, s, a, (int)ntiles, GX, GY);
+  auto kern = p.family == kPersCarry ? kern_c : a.stat_part ? kern_s : kern_d;
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), lds, s, a, p.gx * p.gy, p.gx, p.gy);
   S2S_LAUNCH_CHECK();
   return S2S_OK;
 }
@@ -1863,13 +1690,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_stage_kernel(Conv3x3Args a, in
   }
 }
 
-// Does this bf16 launch run on the staged kernel, and on how many workgroups?  (dispatch() and s2s_conv3x3_stat_rows()
-// share the decision: a statistics launch writes grid x 8 rows.)  0 = no.
-inline int stage_grid(const Conv3x3Args& a, bool stats) {
+// Does this bf16 launch run on the staged kernel, and on how many workgroups?  (A statistics launch writes grid x 8
+// rows.)  0 = no.
+inline int stage_grid(const Conv3x3Args& a, bool stats, bool split) {
   static const int on = [] { const char* e = getenv("S2S_CONV_STAGE"); return e ? atoi(e) : 1; }();
   // (a folded affine -- the eval-mode forward -- has its own instantiation; a bias alone or statistics beside an affine do not)
-  if (!on || (a.c1 && a.c0 % 32) || (a.bias && !a.ep_scale) || (a.ep_scale && stats) || a.kpart || a.act || a.y2 ||
-      !a.direct_ep || (a.dbg & 64)) return 0;
+  if (!on || (a.c1 && a.c0 % 32) || (a.bias && !a.ep_scale) || (a.ep_scale && stats) || split || a.act || a.y2 ||
+      (a.dbg & 64)) return 0;
   if ((double)a.B * a.H * a.W * a.ld0 * 2 >= 4.0e9 || (double)a.B * a.H * a.W * (a.c1 ? a.ld1 : 0) * 2 >= 4.0e9 ||
       (double)a.B * a.H * a.W * a.ldy * 2 >= 2.0e9) return 0;          // 32-bit byte offsets into each tensor (the store's
                                                                          // scalar offset is formed in signed arithmetic)
@@ -1890,57 +1717,38 @@ inline int stage_grid(const Conv3x3Args& a, bool stats) {
   return slots;
 }
 
-inline int launch_stage(Conv3x3Args& a, int grid, hipStream_t s) {
+inline int launch_stage(Conv3x3Args& a, const Conv3x3Plan& p, hipStream_t s) {
   constexpr int lds = 2 * (41 * 1024 + 9 * 4096);
   static_assert(lds <= 160 * 1024, "LDS budget");
   a.tilesY = cdiv(a.H, 16);
   a.tilesX = cdiv(a.W, 32);
-  const bool resident = a.c0 + a.c1 <= 64;             // one or two chunks: the whole filter fits the two stages
+  const bool resident = p.family == kStageResident;
   const int form = a.stat_part ? 1 : (a.ep_scale ? 2 : 0);
   auto kern = form == 1 ? (resident ? conv3x3_stage_kernel<2, false, true> : conv3x3_stage_kernel<2, false, false>)
             : form == 2 ? (resident ? conv3x3_stage_kernel<0, false, true, true> : conv3x3_stage_kernel<0, false, false, true>)
                         : (resident ? conv3x3_stage_kernel<0, true, true> : conv3x3_stage_kernel<0, true, false>);
   static unsigned long long attr[6] = {0, 0, 0, 0, 0, 0};
   if (int rc = s2s_allow_dyn_lds(reinterpret_cast<const void*>(kern), lds, &attr[form * 2 + (resident ? 1 : 0)])) return rc;
-  const int GX = a.B * a.tilesY * a.tilesX, GY = cdiv(a.Cout, 64);
-  a.xsp = GX % 8 == 0 ? 8 : 0; a.xsn = 1;
-  a.stat_carry = a.stat_part != nullptr;
-  a.stat_rows = (long)grid * 8;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a, GX * GY, GX, GY);
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(512), lds, s, a, p.gx * p.gy, p.gx, p.gy);
   S2S_LAUNCH_CHECK();
   return S2S_OK;
 }
 
-template <int TH, int TW, int BN, int WM, int WN, int NS>
-int launch_dma16(Conv3x3Args& a, hipStream_t s) {
+// weight ring depth: four slots everywhere (eight gave the 64-channel tiles nothing: 250 vs 242 us on 192 -> 64, round 3)
+template <int ID>
+int launch_dma16(Conv3x3Args& a, const Conv3x3Plan& p, hipStream_t s) {
+  constexpr TileCfg c = kBf16Cfg[ID];
+  constexpr int TH = c.th, TW = c.tw, BN = c.bn, WM = c.wm, WN = 4 / WM, NS = 4;
   constexpr int ROWS = (TH + 2) * (TW + 4);
   constexpr int HG = ((ROWS + 15) / 16 + 3) / 4;
-  constexpr int lds = 2 * HG * 4 * 1024 + NS * BN * 64;      // the epilogue stages inside this (static_assert there)
+  constexpr int lds = 2 * HG * 4 * 1024 + NS * BN * 64;
   static_assert(lds <= 160 * 1024, "LDS budget");
   a.tilesY = cdiv(a.H, TH);
   a.tilesX = cdiv(a.W, TW);
   auto kern = conv3x3_dma16_kernel<TH, TW, BN, WM, WN, NS>;
   static unsigned long long attr_devs = 0;   // hipFuncSetAttribute is per device
   if (int rc = s2s_allow_dyn_lds(reinterpret_cast<const void*>(kern), lds, &attr_devs)) return rc;
-  if (!a.kpart) a.ksplit = 1;
-  dim3 grid(a.B * a.tilesY * a.tilesX, cdiv(a.Cout, BN), a.ksplit);
-  a.stat_rows = (long)grid.x * (a.direct_ep ? WM : 1);      // (s2s_conv3x3_stat_blocks reports the same count)
-  if (a.stat_part && a.stat_rows_req && a.stat_rows_req != a.stat_rows) return S2S_ERR_SHAPE;
-  static const int xcd_aware = [] { const char* e = getenv("S2S_CONV_XCD"); return e ? atoi(e) : 1; }();
-  a.xsp = 0; a.xsn = 1;
-  if (xcd_aware && a.ksplit == 1 && ((long)grid.x * grid.y) % 8 == 0) {
-    // bytes the 8 L2s fetch between them: an XCD reads the activations of its pixel range and the weights of its
-    // channel range, so the grid cut (sp pixel ranges x sn channel ranges) costs sn * |activations| + sp * |weights|
-    const double act = 2.0 * a.B * a.H * a.W * (a.c0 + a.c1), wb = 2.0 * 9 * (a.c0 + a.c1) * a.Cout;
-    double best = 0;
-    for (int sp = 8; sp >= 1; sp >>= 1) {
-      const int sn = 8 / sp;
-      if (grid.x % sp || grid.y % sn) continue;
-      const double cost = sn * act + sp * wb;
-      if (!a.xsp || cost < best) { best = cost; a.xsp = sp; a.xsn = sn; }
-    }
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
+  hipLaunchKernelGGL(kern, dim3(p.gx, p.gy, p.ksplit), dim3(256), lds, s, a);
   S2S_LAUNCH_CHECK();
   return S2S_OK;
 }
@@ -2165,9 +1973,10 @@ __global__ __launch_bounds__(256, 2) void convkxk_dma16_kernel(Conv3x3Args a) {
     }
     return;
   }
-  // (per-tile statistics rows are only defined for the single-phase forms)
-  const long stat_row = MODE == 2 ? -1 : (long)blockIdx.x;
-  if (!a.stat_part && a.direct_ep) {
+  // statistics (one row per tile) are only taken by the single-phase forms: s2s_conv4x4s2_nhwc / s2s_convt4x4s2_nhwc
+  // (MODE 1 / 2) pass none
+  const long stat_row = blockIdx.x;
+  if (MODE != 0 || !a.stat_part) {
     if (a.ep_scale) conv_epilogue16_direct<TH, TW, BN, WM, WN, true>(a, acc, biasr, img, y0, x0p, n0, tid, om);
     else conv_epilogue16_direct<TH, TW, BN, WM, WN, false>(a, acc, biasr, img, y0, x0p, n0, tid, om);
   } else if (a.ep_scale) conv_epilogue16<TH, TW, BN, WM, WN, 2 * A_BYTES + NS * B_BYTES, true>(a, acc, biasr, smem, img, y0, x0p, n0, tid, stat_row, om);
@@ -2415,31 +2224,6 @@ __global__ __launch_bounds__(256) void convk_splitk_reduce_kernel(Conv3x3Args a,
   }
 }
 
-#ifdef S2S_ABLATE
-template <int TH, int TW, int BN, int WM, int WN, int NS>
-int launch_dma(Conv3x3Args& a, hipStream_t s) {
-  constexpr int ROWS = (TH + 2) * (TW + 4);
-  constexpr int HG = ((ROWS + 15) / 16 + 3) / 4;
-  constexpr int lds_main = 2 * HG * 4 * 1024 + NS * BN * 64;
-  constexpr int RS_ = BN * 2 + 64;
-  constexpr int red_ = WM * 2 * BN * 4;
-  constexpr int EP_ = (TH * TW * RS_ + red_ <= lds_main) ? 1 : ((TH * TW / 2) * RS_ + red_ <= lds_main ? 2 : 4);
-  constexpr int lds_epi = (TH * TW / EP_) * RS_ + red_;
-  constexpr int lds = lds_main > lds_epi ? lds_main : lds_epi;
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  a.tilesY = cdiv(a.H, TH);
-  a.tilesX = cdiv(a.W, TW);
-  auto kern = conv3x3_dma_kernel<TH, TW, BN, WM, WN, NS>;
-  static unsigned long long attr_devs = 0;   // hipFuncSetAttribute is per device
-  if (int rc = s2s_allow_dyn_lds(reinterpret_cast<const void*>(kern), lds, &attr_devs)) return rc;
-  dim3 grid(a.B * a.tilesY * a.tilesX, cdiv(a.Cout, BN));
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
-  S2S_LAUNCH_CHECK();
-  return S2S_OK;
-}
-
-#endif  // S2S_ABLATE
-
 template <typename T, int TH, int TW, int BN, int WM, int WN, int KS = 3, int PAD = 1>
 int launch_cfg(Conv3x3Args& a, hipStream_t s) {
   constexpr bool SPLIT = std::is_same<T, float>::value;
@@ -2599,116 +2383,127 @@ int launch_stem(Conv3x3Args& a, const float* x, const float* w, int Cin, hipStre
   return S2S_OK;
 }
 
-// ---- tile configuration table -----------------------------------------------------------------------
-// The largest tile whose grid still gives every CU about two workgroups wins; small feature maps
-// (16x16 ... 32x32 at batch 16) fall through to smaller tiles so that the 256 CUs stay busy.
-struct TileCfg { int th, tw, bn; };
-constexpr TileCfg kBf16Cfg[8] = {{8, 32, 128}, {8, 32, 64}, {4, 32, 128}, {4, 32, 64},
-                                 {16, 16, 128}, {16, 16, 64}, {8, 16, 128}, {8, 16, 64}};
-constexpr TileCfg kF32Cfg[2] = {{4, 32, 64}, {8, 16, 64}};
-constexpr int kMinBlocks = 448;
-
-inline long cfg_blocks(const TileCfg& c, int B, int H, int W, int Cout) {
-  return (long)B * cdiv(H, c.th) * cdiv(W, c.tw) * cdiv(Cout, c.bn);
-}
-
-int select_cfg(int dtype, int B, int H, int W, int Cout) {
-  if (dtype == S2S_F32) return W <= 16 ? 1 : 0;
-  const char* force = getenv("S2S_CONV_CFG");
-  if (force && force[0] >= '0' && force[0] <= '7') return force[0] - '0';
-  const int first = W <= 16 ? 4 : 0;
-  int best = -1;
-  long best_blocks = -1;
-  for (int i = first; i < first + 4; ++i) {
-    const TileCfg& c = kBf16Cfg[i];
-    if (c.bn == 128 && (Cout <= 64 || (Cout % 128 != 0 && Cout % 128 <= 64 && Cout < 512))) continue;   // half-empty N tile
-    const long nb = cfg_blocks(c, B, H, W, Cout);
-    if (nb >= kMinBlocks) return i;
-    if (nb > best_blocks) { best_blocks = nb; best = i; }
-  }
-  return best;
-}
-
-// Does this bf16 launch run on the persistent kernel?  (dispatch() and s2s_conv3x3_stat_rows() share the decision: the
-// number of statistics rows follows it.)
-inline bool pers_eligible(const Conv3x3Args& a, int id) {
+// Does this bf16 launch run on the persistent kernel?
+inline bool pers_eligible(const Conv3x3Args& a, int id, bool split) {
   static const int pers = [] { const char* e = getenv("S2S_CONV_PERS"); return e ? atoi(e) : 1; }();
   // (only where a workgroup gets at least two tiles on average: with one tile each the walk buys nothing and its
   //  bookkeeping costs 3-10 % -- measured on the 64^2 / 32^2 levels, whose grids are ~512 tiles)
-  if (id == 0 || id == 4) return false;      // 256-pixel x 128-channel tiles spill in the tile walk: one-tile kernel
   const TileCfg& tc = kBf16Cfg[id];
+  if (!tc.pers) return false;
   const bool many = cfg_blocks(tc, a.B, a.H, a.W, a.Cout) >= (pers > 1 ? pers : 1024);
-  return pers && many && a.direct_ep && !a.bias && !a.ep_scale && !a.kpart && !a.act && !a.y2 && a.nchunk >= 2 && !(a.dbg & 64) &&
+  return pers && many && !a.bias && !a.ep_scale && !split && !a.act && !a.y2 && a.nchunk >= 2 && !(a.dbg & 64) &&
          a.c0 % 32 == 0 &&                      // a chunk reads one source; 32-bit byte offsets into each source
          (double)a.B * a.H * a.W * a.ld0 * 2 < 4.0e9 && (double)a.B * a.H * a.W * (a.c1 ? a.ld1 : 0) * 2 < 4.0e9;
 }
 
+// XCD cut of a GX x GY tile grid (p.xsp x p.xsn; left at 0 x 1 when no cut divides the grid).  Bytes the 8 L2s fetch
+// between them: an XCD reads the activations of its pixel range and the weights of its channel range, so the cut into
+// sp pixel ranges x sn channel ranges costs sn * |activations| + sp * |weights|.
+inline void xcd_cut(const Conv3x3Args& a, int GX, int GY, Conv3x3Plan& p) {
+  const double act = 2.0 * a.B * a.H * a.W * (a.c0 + a.c1), wb = 2.0 * 9 * (a.c0 + a.c1) * a.Cout;
+  double best = 0;
+  for (int sp = 8; sp >= 1; sp >>= 1) {
+    const int sn = 8 / sp;
+    if (GX % sp || GY % sn) continue;
+    const double cost = sn * act + sp * wb;
+    if (!p.xsp || cost < best) { best = cost; p.xsp = sp; p.xsn = sn; }
+  }
+}
+
+// K splits of a launch without statistics that is given a workspace: at small batch the deep levels have a few dozen
+// output tiles and K = 9 x 512..1536, so the chunk range is shared by up to 16 workgroups.
+inline int split_count(long tiles, int nchunk) {
+  if (tiles >= 128 || nchunk < 8) return 1;
+  long sp = (512 + tiles - 1) / tiles;
+  if (sp > nchunk / 4) sp = nchunk / 4;
+  if (sp > 16) sp = 16;
+  return sp < 2 ? 1 : (int)sp;
+}
+
+// stat_rows_req of a query: whichever statistics layout the launch prefers (s2s_conv3x3_stat_rows)
+constexpr long kAnyRows = -1;
+
+// The one place that decides a 3x3 launch.  Inputs besides the shapes: which operands exist (bias, ep_scale, act, y2,
+// stat_part; kpart = a split workspace is offered), stat_rows_req and the S2S_CONV_* switches.
+Conv3x3Plan conv3x3_plan(int dtype, const Conv3x3Args& a) {
+  const bool stats = a.stat_part != nullptr;
+  const long req = a.stat_rows_req;
+  Conv3x3Plan p{};
+  p.rc = S2S_OK; p.xsn = 1; p.ksplit = 1;
+  p.cfg = select_cfg(dtype, a.B, a.H, a.W, a.Cout);
+  const TileCfg& c = dtype == S2S_F32 ? kF32Cfg[p.cfg] : kBf16Cfg[p.cfg];
+  p.gx = a.B * cdiv(a.H, c.th) * cdiv(a.W, c.tw);
+  p.gy = cdiv(a.Cout, c.bn);
+  if (dtype == S2S_F32) {     // one statistics row per tile (gridDim.x, conv_epilogue); stat_rows_req is not checked
+    p.family = kSplitF32;
+    p.stat_rows = p.gx;
+    return p;
+  }
+  if (a.kpart && !stats) p.ksplit = split_count((long)p.gx * p.gy, a.nchunk);
+  const bool split = p.ksplit > 1;
+  // many tiles: the staged kernel, one barrier per chunk (statistics launches only when the caller sized stat_part for it:
+  // the sums are carried per (workgroup, wave row))
+  if (const int wg = stage_grid(a, stats, split)) {
+    if (!stats || req == kAnyRows || req == (long)wg * 8) {
+      p.family = a.c0 + a.c1 <= 64 ? kStageResident : kStageStream;   // one or two chunks: the filter fits the two stages
+      p.gx = a.B * cdiv(a.H, 16) * cdiv(a.W, 32);
+      p.gy = cdiv(a.Cout, 64);
+      p.grid = wg;
+      p.xsp = p.gx % 8 == 0 ? 8 : 0;
+      p.stat_rows = (long)wg * 8;
+      return p;
+    }
+  }
+  if (pers_eligible(a, p.cfg, split)) {
+    // the training step's launches (forward with BatchNorm statistics, data gradients: no bias, no folded affine, no
+    // split-K) walk their tiles on the persistent kernel; S2S_CONV_PERS=0: one tile per workgroup as before
+    const long ntiles = (long)p.gx * p.gy;
+    if (ntiles % 8 == 0) xcd_cut(a, p.gx, p.gy, p);
+    constexpr int slots = 512;                           // 2 per CU (swept in round 3: no better grid)
+    int grid = (int)(ntiles < slots ? ntiles : slots);
+    if (p.xsp && grid > 8) grid -= grid % 8;             // a stride that is a multiple of 8 keeps a workgroup inside its XCD's block
+    p.grid = grid < 1 ? 1 : grid;
+    // statistics rows: one per (workgroup, wave row) when the caller sized the buffer for that and there is a single
+    // channel tile; else one per (tile, wave row)
+    const bool carry = stats && p.gy == 1 && (req == kAnyRows || req == (long)p.grid * c.wm);
+    p.family = carry ? kPersCarry : kPers;
+    p.stat_rows = (long)(carry ? p.grid : p.gx) * c.wm;
+  } else {
+    static const int xcd_aware = [] { const char* e = getenv("S2S_CONV_XCD"); return e ? atoi(e) : 1; }();
+    p.family = kTap;
+    p.stat_rows = (long)p.gx * c.wm;
+    if (xcd_aware && !split && ((long)p.gx * p.gy) % 8 == 0) xcd_cut(a, p.gx, p.gy, p);
+  }
+  if (stats && req > 0 && req != p.stat_rows) p.rc = S2S_ERR_SHAPE;
+  return p;
+}
+
+// f(std::integral_constant<int, id>{}): a kBf16Cfg index as a template argument
+template <int ID = 0, typename F>
+int with_cfg(int id, F&& f) {
+  if constexpr (ID < 8) return id == ID ? f(std::integral_constant<int, ID>{}) : with_cfg<ID + 1>(id, f);
+  else return S2S_ERR_SHAPE;
+}
+
 int dispatch(int dtype, Conv3x3Args& a, hipStream_t s) {
-  const int id = select_cfg(dtype, a.B, a.H, a.W, a.Cout);
-  if (dtype == S2S_F32) {
-    // three bf16 images per operand: small tiles so the double-buffered LDS still fits
-    if (id == 1) return launch_cfg<float, 8, 16, 64, 2, 2>(a, s);
-    return launch_cfg<float, 4, 32, 64, 2, 2>(a, s);
+  const Conv3x3Plan p = conv3x3_plan(dtype, a);
+  if (p.rc != S2S_OK) return p.rc;
+  a.xsp = p.xsp; a.xsn = p.xsn; a.ksplit = p.ksplit; a.stat_rows = p.stat_rows;
+  if (p.ksplit == 1) a.kpart = nullptr;
+  switch (p.family) {
+    case kSplitF32:      // three bf16 images per operand: small tiles so the double-buffered LDS still fits
+      return p.cfg == 1 ? launch_cfg<float, 8, 16, 64, 2, 2>(a, s) : launch_cfg<float, 4, 32, 64, 2, 2>(a, s);
+    case kStageResident:
+    case kStageStream: return launch_stage(a, p, s);
+    case kPersCarry:
+    case kPers:
+      return with_cfg(p.cfg, [&](auto id) {
+        constexpr int ID = decltype(id)::value;
+        if constexpr (kBf16Cfg[ID].pers) return launch_pers16<ID>(a, p, s);
+        else return S2S_ERR_SHAPE;
+      });
+    default: return with_cfg(p.cfg, [&](auto id) { return launch_dma16<decltype(id)::value>(a, p, s); });
   }
-  // bf16: the LDS-DMA loop on v_mfma_f32_16x16x32_bf16.  (Ablation builds, -DS2S_ABLATE, additionally honour
-  // S2S_CONV_DMA = 1/3: the 32x32x16 form with a 4/3-slot ring, 0: the register-staged v1 loop.)
-#ifdef S2S_ABLATE
-  static const int use_dma = [] { const char* e = getenv("S2S_CONV_DMA"); return e ? atoi(e) : 16; }();
-  if (use_dma != 16 && use_dma) {
-    switch (id) {
-      case 0: return use_dma == 3 ? launch_dma<8, 32, 128, 2, 2, 3>(a, s) : launch_dma<8, 32, 128, 2, 2, 4>(a, s);
-      case 1: return use_dma == 3 ? launch_dma<8, 32, 64, 4, 1, 3>(a, s) : launch_dma<8, 32, 64, 4, 1, 4>(a, s);
-      case 2: return use_dma == 3 ? launch_dma<4, 32, 128, 2, 2, 3>(a, s) : launch_dma<4, 32, 128, 2, 2, 4>(a, s);
-      case 3: return use_dma == 3 ? launch_dma<4, 32, 64, 2, 2, 3>(a, s) : launch_dma<4, 32, 64, 2, 2, 4>(a, s);
-      case 4: return use_dma == 3 ? launch_dma<16, 16, 128, 2, 2, 3>(a, s) : launch_dma<16, 16, 128, 2, 2, 4>(a, s);
-      case 5: return use_dma == 3 ? launch_dma<16, 16, 64, 4, 1, 3>(a, s) : launch_dma<16, 16, 64, 4, 1, 4>(a, s);
-      case 6: return use_dma == 3 ? launch_dma<8, 16, 128, 2, 2, 3>(a, s) : launch_dma<8, 16, 128, 2, 2, 4>(a, s);
-      case 7: return use_dma == 3 ? launch_dma<8, 16, 64, 2, 2, 3>(a, s) : launch_dma<8, 16, 64, 2, 2, 4>(a, s);
-    }
-  }
-  if (!use_dma) {
-    switch (id) {
-      case 0: return launch_cfg<bf16_t, 8, 32, 128, 2, 2>(a, s);
-      case 1: return launch_cfg<bf16_t, 8, 32, 64, 4, 1>(a, s);
-      case 2: return launch_cfg<bf16_t, 4, 32, 128, 2, 2>(a, s);
-      case 3: return launch_cfg<bf16_t, 4, 32, 64, 2, 2>(a, s);
-      case 4: return launch_cfg<bf16_t, 16, 16, 128, 2, 2>(a, s);
-      case 5: return launch_cfg<bf16_t, 16, 16, 64, 4, 1>(a, s);
-      case 6: return launch_cfg<bf16_t, 8, 16, 128, 2, 2>(a, s);
-      case 7: return launch_cfg<bf16_t, 8, 16, 64, 2, 2>(a, s);
-    }
-  }
-#endif
-  // the training step's launches (forward with BatchNorm statistics, data gradients: no bias, no folded affine, no
-  // split-K) run on the persistent kernel; S2S_CONV_PERS=0: one tile per workgroup as before
-  // many tiles: the staged kernel, one barrier per chunk (statistics launches only when the caller sized stat_part for it)
-  if (const int wg = stage_grid(a, a.stat_part != nullptr)) {
-    if (!a.stat_part || a.stat_rows_req == (long)wg * 8) return launch_stage(a, wg, s);
-  }
-  if (pers_eligible(a, id)) {
-    switch (id) {      // (the 256-pixel x 128-channel tiles, ids 0 and 4, need 128 accumulator + 48 fragment registers: with the
-                       //  tile loop's state they spill, so they stay on the one-tile-per-workgroup kernel)
-      case 1: return launch_pers16<8, 32, 64, 4, 1>(a, s);
-      case 2: return launch_pers16<4, 32, 128, 2, 2>(a, s);
-      case 3: return launch_pers16<4, 32, 64, 2, 2>(a, s);
-      case 5: return launch_pers16<16, 16, 64, 4, 1>(a, s);
-      case 6: return launch_pers16<8, 16, 128, 2, 2>(a, s);
-      case 7: return launch_pers16<8, 16, 64, 2, 2>(a, s);
-      default: break;
-    }
-  }
-  // weight ring depth: four slots everywhere (eight gave the 64-channel tiles nothing: 250 vs 242 us on 192 -> 64, round 3)
-  switch (id) {
-    case 0: return launch_dma16<8, 32, 128, 2, 2, 4>(a, s);
-    case 1: return launch_dma16<8, 32, 64, 4, 1, 4>(a, s);
-    case 2: return launch_dma16<4, 32, 128, 2, 2, 4>(a, s);
-    case 3: return launch_dma16<4, 32, 64, 2, 2, 4>(a, s);
-    case 4: return launch_dma16<16, 16, 128, 2, 2, 4>(a, s);
-    case 5: return launch_dma16<16, 16, 64, 4, 1, 4>(a, s);
-    case 6: return launch_dma16<8, 16, 128, 2, 2, 4>(a, s);
-    case 7: return launch_dma16<8, 16, 64, 2, 2, 4>(a, s);
-  }
-  return S2S_ERR_SHAPE;
 }
 
 }  // namespace
@@ -2720,15 +2515,13 @@ int s2s_internal_stem_fwd(int dtype, const float* x_nchw, const float* w_oihw, c
   a.x0 = a.x1 = a.w = nullptr; a.bias = bias; a.y = y; a.stat_part = stat_part;
   a.ep_scale = a.ep_shift = nullptr; a.act = 0; a.act_slope = 0.f; a.y2 = nullptr; a.ldy2 = 8; a.bias_mod = Cout;
   a.ld0 = a.c0 = a.ld1 = a.c1 = 0; a.ldy = ldy;
-  a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.nchunk = 1; a.relu = 0; a.dbg = 0; a.direct_ep = direct_ep_default();
+  a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.nchunk = 1; a.relu = 0; a.dbg = 0;
   a.tilesX = a.tilesY = 0;
   if (dtype == S2S_BF16) return launch_stem<bf16_t>(a, x_nchw, w_oihw, Cin, s);
   if (dtype == S2S_F32) return launch_stem<float>(a, x_nchw, w_oihw, Cin, s);
   return S2S_ERR_DTYPE;
 }
 
-// Number of row-blocks of partial statistics the kernel writes for a (B,H,W,Cout) problem
-// (= gridDim.x); the caller sizes stat_part as [2][Cout][blocks] floats.
 // out: HOST buffer long[n][4] = {shader clock at entry, at exit, wall clock (100 MHz) at entry, at exit} of the
 // first n <= 8192 workgroups of the last conv3x3 launch made with S2S_CONV_DBG=64
 extern "C" int s2s_debug_conv_clock(long* out, int n) {
@@ -2738,20 +2531,38 @@ extern "C" int s2s_debug_conv_clock(long* out, int n) {
                                                                                                   : S2S_ERR_LAUNCH;
 }
 
+static void conv3x3_fill_args(Conv3x3Args& a, int ld0, int c0, int ld1, int c1, const float* bias, int B, int H, int W,
+                              int Cout) {
+  a.bias = bias;
+  a.act = 0; a.act_slope = 0.f; a.y2 = nullptr; a.ldy2 = 8; a.bias_mod = Cout; a.kpart = nullptr; a.ksplit = 1; a.lgc = 0; a.lgh = a.lgw = 0;
+  a.ld0 = ld0; a.c0 = c0; a.ld1 = ld1; a.c1 = c1;
+  a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.nchunk = cdiv(c0 + c1, 32);
+  a.tilesX = a.tilesY = 0;
+  // S2S_CONV_DBG: 64 = clock probe (leaves the results unchanged); the result-changing timing ablations (bits 1-32)
+  // exist only in -DS2S_ABLATE builds
+  { static const int dbg = [] { const char* e = getenv("S2S_CONV_DBG"); return (e ? atoi(e) : 0) & S2S_DBG_MASK; }(); a.dbg = dbg; }
+}
+
+// The plan of a launch of these operands, for the queries below: nothing is launched, so bias, stat_part and the split
+// workspace only need to be present or absent.
+static Conv3x3Plan conv3x3_query(int dtype, int B, int H, int W, int Cout, int c0, int c1, int ld0, int ld1, int ldy,
+                                 bool bias, bool stats, long stat_rows_req, bool kwork) {
+  static float present;
+  Conv3x3Args a{};
+  conv3x3_fill_args(a, ld0, c0, ld1, c1, bias ? &present : nullptr, B, H, W, Cout);
+  a.ldy = ldy;
+  a.stat_part = stats ? &present : nullptr;
+  a.stat_rows_req = stat_rows_req;
+  a.kpart = kwork ? &present : nullptr;
+  return conv3x3_plan(dtype, a);
+}
+
+// Rows of partial statistics per channel that a launch passed stat_rows = 0 writes (the per-tile layout, which depends on
+// the output shape alone); the caller sizes stat_part as [2][Cout][rows] floats.
 extern "C" int s2s_conv3x3_stat_blocks(int dtype, int B, int H, int W, int Cout) {
   if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0) return S2S_ERR_SHAPE;
   if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
-  const int id = select_cfg(dtype, B, H, W, Cout);
-  const TileCfg& c = dtype == S2S_F32 ? kF32Cfg[id] : kBf16Cfg[id];
-  const int tiles = B * cdiv(H, c.th) * cdiv(W, c.tw);
-  if (dtype == S2S_F32 || !direct_ep_default()) return tiles;
-#ifdef S2S_ABLATE
-  { static const int use_dma = [] { const char* e = getenv("S2S_CONV_DMA"); return e ? atoi(e) : 16; }();
-    if (use_dma != 16) return tiles; }
-#endif
-  // the register epilogue of the bf16 kernel writes one row per (tile, wave row): WM = 4 for the 64-wide 4 x 1 tiles
-  static const int wm_of[8] = {2, 4, 2, 2, 2, 4, 2, 2};
-  return tiles * wm_of[id];
+  return (int)conv3x3_query(dtype, B, H, W, Cout, 0, 0, 0, 0, 0, false, true, 0, false).stat_rows;
 }
 
 extern "C" int s2s_conv3x3_nhwc_k(int dtype, const void* x0, int ld0, int c0, const void* x1, int ld1, int c1,
@@ -2763,24 +2574,12 @@ extern "C" int s2s_conv3x3_nhwc_s(int dtype, const void* x0, int ld0, int c0, co
                                   const float* ep_scale, const float* ep_shift, int relu, float* kwork, int B, int H,
                                   int W, int Cout, void* stream);
 
-// Split count of s2s_conv3x3_nhwc_k for a launch without statistics (bf16; 1 = not split): at small batch the deep
-// levels have a few dozen output tiles and K = 9 x 512..1536, so the chunk range is shared by up to 16 workgroups.
+// Split count of s2s_conv3x3_nhwc_k for a launch without statistics (bf16; 1 = not split; split_count).
 // kwork: float[splits][B*H*W][Cout].
 extern "C" int s2s_conv3x3_ksplit(int dtype, int B, int H, int W, int Cout, int cin) {
   if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || cin <= 0) return S2S_ERR_SHAPE;
   if (dtype != S2S_BF16) return 1;
-#ifdef S2S_ABLATE
-  static const int use_dma = [] { const char* e = getenv("S2S_CONV_DMA"); return e ? atoi(e) : 16; }();
-  if (use_dma != 16) return 1;
-#endif
-  const TileCfg& c = kBf16Cfg[select_cfg(dtype, B, H, W, Cout)];
-  const long base = cfg_blocks(c, B, H, W, Cout);
-  const int nchunk = cdiv(cin, 32);
-  if (base >= 128 || nchunk < 8) return 1;
-  long sp = (512 + base - 1) / base;
-  if (sp > nchunk / 4) sp = nchunk / 4;
-  if (sp > 16) sp = 16;
-  return sp < 2 ? 1 : (int)sp;
+  return conv3x3_query(dtype, B, H, W, Cout, cin, 0, 0, 0, 0, false, false, 0, true).ksplit;
 }
 
 extern "C" int s2s_conv3x3_nhwc(int dtype, const void* x0, int ld0, int c0, const void* x1, int ld1, int c1,
@@ -2791,52 +2590,23 @@ extern "C" int s2s_conv3x3_nhwc(int dtype, const void* x0, int ld0, int c0, cons
                             nullptr, B, H, W, Cout, stream);
 }
 
-static void conv3x3_fill_args(Conv3x3Args& a, int ld0, int c0, int ld1, int c1, const float* bias, int B, int H, int W,
-                              int Cout) {
-  a.bias = bias;
-  a.act = 0; a.act_slope = 0.f; a.y2 = nullptr; a.ldy2 = 8; a.bias_mod = Cout; a.kpart = nullptr; a.ksplit = 1; a.lgc = 0; a.lgh = a.lgw = 0;
-  a.ld0 = ld0; a.c0 = c0; a.ld1 = ld1; a.c1 = c1;
-  a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.nchunk = cdiv(c0 + c1, 32);
-  a.tilesX = a.tilesY = 0;
-  // S2S_CONV_DBG: 64 = clock probe, 128 = the earlier LDS slot key (both leave the results unchanged); the
-  // result-changing timing ablations (bits 1-32) exist only in -DS2S_ABLATE builds
-  { static const int dbg = [] { const char* e = getenv("S2S_CONV_DBG"); return (e ? atoi(e) : 0) & S2S_DBG_MASK; }(); a.dbg = dbg; }
-  a.direct_ep = direct_ep_default();
-}
-
 // Rows of BatchNorm partial sums a TRAINING-step launch (statistics, no folded affine, no split) of these operands
-// writes: s2s_conv3x3_stat_blocks() of them, or -- when the launch runs on the persistent kernel with one channel tile --
-// one per (workgroup, wave row).  Size stat_part as float[2][Cout][rows] and pass `rows` to s2s_conv3x3_nhwc_s.
+// writes: s2s_conv3x3_stat_blocks() of them, or -- when the launch runs on the staged kernel, or on the persistent kernel
+// with one channel tile -- one per (workgroup, wave row).  Size stat_part as float[2][Cout][rows] and pass `rows` to
+// s2s_conv3x3_nhwc_s.
 extern "C" int s2s_conv3x3_stat_rows(int dtype, int B, int H, int W, int Cout, int c0, int c1, int ld0, int ld1,
                                      int has_bias) {
-  const int legacy = s2s_conv3x3_stat_blocks(dtype, B, H, W, Cout);
-  if (legacy < 0 || dtype != S2S_BF16 || c0 <= 0 || c1 < 0) return legacy;
-#ifdef S2S_ABLATE
-  { static const int use_dma = [] { const char* e = getenv("S2S_CONV_DMA"); return e ? atoi(e) : 16; }();
-    if (use_dma != 16) return legacy; }
-#endif
-  Conv3x3Args a{};
-  static const float one = 1.f;
-  conv3x3_fill_args(a, ld0, c0, ld1, c1, has_bias ? &one : nullptr, B, H, W, Cout);
-  if (const int wg = stage_grid(a, true)) return wg * 8;
-  const int id = select_cfg(dtype, B, H, W, Cout);
-  if (!pers_eligible(a, id)) return legacy;
-  const TileCfg& tc = kBf16Cfg[id];
-  const int GX = B * cdiv(H, tc.th) * cdiv(W, tc.tw), GY = cdiv(Cout, tc.bn);
-  if (GY != 1) return legacy;
-  static const int wm_of[8] = {2, 4, 2, 2, 2, 4, 2, 2};
-  return pers_plan(a, GX, GY).grid * wm_of[id];
+  const int tiles = s2s_conv3x3_stat_blocks(dtype, B, H, W, Cout);
+  if (tiles < 0 || c0 <= 0 || c1 < 0) return tiles;
+  return (int)conv3x3_query(dtype, B, H, W, Cout, c0, c1, ld0, ld1, 0, has_bias, true, kAnyRows, false).stat_rows;
 }
 
 extern "C" int s2s_conv3x3_staged(int dtype, int B, int H, int W, int Cout, int c0, int c1, int ld0, int ld1, int ldy,
                                   int stats) {
   if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || c0 <= 0 || c1 < 0) return S2S_ERR_SHAPE;
   if (dtype != S2S_BF16) return 0;
-  Conv3x3Args a{};
-  conv3x3_fill_args(a, ld0, c0, ld1, c1, nullptr, B, H, W, Cout);
-  a.ldy = ldy;
-  if (!stage_grid(a, stats != 0)) return 0;
-  return c0 + c1 <= 64 ? 2 : 1;
+  const int f = conv3x3_query(dtype, B, H, W, Cout, c0, c1, ld0, ld1, ldy, false, stats != 0, kAnyRows, false).family;
+  return f == kStageResident ? 2 : f == kStageStream ? 1 : 0;
 }
 
 extern "C" int s2s_conv3x3_nhwc_k(int dtype, const void* x0, int ld0, int c0, const void* x1, int ld1, int c1,
@@ -2867,8 +2637,7 @@ extern "C" int s2s_conv3x3_nhwc_s(int dtype, const void* x0, int ld0, int c0, co
   a.ep_scale = ep_scale; a.ep_shift = ep_shift; a.ldy = ldy; a.relu = relu;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
-  a.ksplit = (kwork && !stat_part) ? s2s_conv3x3_ksplit(dtype, B, H, W, Cout, c0 + c1) : 1;
-  a.kpart = a.ksplit > 1 ? kwork : nullptr;
+  a.kpart = kwork;                                     // dispatch() keeps it for a split launch only
   const int rc = dispatch(dtype, a, s);
   if (rc != S2S_OK || !a.kpart) return rc;
   const long npix = (long)B * H * W, pieces = npix * (Cout / 8);
@@ -2878,7 +2647,6 @@ extern "C" int s2s_conv3x3_nhwc_s(int dtype, const void* x0, int ld0, int c0, co
   S2S_LAUNCH_CHECK();
   return S2S_OK;
 }
-
 // ---- KS x KS-tap convolutions of row a13 -------------------------------------------------------------------------
 // Output H x W, y[i][j] = sum_{a,b < ks} W[a][b] x[i + a - pad][j + b - pad] (zero outside), input (H + ks - 1 - 2 pad):
 //   ks = 2, pad = 0: the 4x4 stride-2 pad-1 convolution, as a 2x2 "valid" convolution over the space-to-depth image of
@@ -2939,7 +2707,7 @@ extern "C" int s2s_convkxk_nhwc(int dtype, const void* x, int ldx, int cin, cons
   a.kpart = a.ksplit > 1 ? kwork : nullptr;
   if (a.kpart && stat_part) return S2S_ERR_SHAPE;                   // split launches do not produce statistics
   a.ld0 = ldx; a.c0 = cin; a.ld1 = 8; a.c1 = 0; a.ldy = ldy;
-  a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.nchunk = cdiv(cin, 32); a.relu = 0; a.dbg = 0; a.direct_ep = direct_ep_default();
+  a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.nchunk = cdiv(cin, 32); a.relu = 0; a.dbg = 0;
   a.tilesX = a.tilesY = 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool wide = W > 16, big = Cout > 64;
@@ -3072,7 +2840,7 @@ extern "C" int s2s_conv4x4s2_nhwc(int dtype, const void* x, int ldx, int Cin, co
   a.ep_scale = a.ep_shift = nullptr; a.act = act ? 1 : 0; a.act_slope = act_slope; a.y2 = y2; a.ldy2 = ldy2;
   a.bias_mod = Cout; a.lgc = __builtin_ctz((unsigned)Cin);
   a.ld0 = ldx; a.c0 = 4 * Cin; a.ld1 = 8; a.c1 = 0; a.ldy = ldy;
-  a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.nchunk = cdiv(4 * Cin, 32); a.relu = 0; a.dbg = 0; a.direct_ep = direct_ep_default();
+  a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.nchunk = cdiv(4 * Cin, 32); a.relu = 0; a.dbg = 0;
   a.tilesX = a.tilesY = 0;
   a.ksplit = kwork ? s2s_conv4x4s2_ksplit(B, H, W, Cout, Cin) : 1;
   a.kpart = a.ksplit > 1 ? kwork : nullptr;
@@ -3121,7 +2889,7 @@ extern "C" int s2s_convt4x4s2_nhwc(int dtype, const void* x, int ldx, int Cin, c
   a.ep_scale = a.ep_shift = nullptr; a.act = 0; a.act_slope = 0.f; a.y2 = nullptr; a.ldy2 = 8;
   a.bias_mod = C; a.lgc = 0;
   a.ld0 = ldx; a.c0 = Cin; a.ld1 = 8; a.c1 = 0; a.ldy = ldy;
-  a.B = B; a.H = h; a.W = w; a.Cout = C; a.nchunk = cdiv(Cin, 32); a.relu = 0; a.dbg = 0; a.direct_ep = direct_ep_default();
+  a.B = B; a.H = h; a.W = w; a.Cout = C; a.nchunk = cdiv(Cin, 32); a.relu = 0; a.dbg = 0;
   a.tilesX = a.tilesY = 0;
   a.ksplit = kwork ? s2s_convt4x4s2_ksplit(B, h, w, C, Cin) : 1;
   a.kpart = a.ksplit > 1 ? kwork : nullptr;

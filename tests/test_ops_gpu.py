@@ -163,6 +163,41 @@ def test_conv3x3_staged_kernel(case):
         assert relerr(s[1], (yb * yb).sum((0, 2, 3))) < 2e-4
 
 
+@pytest.mark.parametrize("case", [(6, 250, 270, 64, 64), (16, 128, 128, 128, 64)])
+def test_conv3x3_stats_per_tile_layout(case):
+    """stat_rows = 0 -- what s2s_conv3x3_nhwc and _nhwc_k pass -- gives the per-tile statistics layout of
+    s2s_conv3x3_stat_blocks, also for launches that s2s_conv3x3_stat_rows puts on a kernel carrying its sums: the staged
+    kernel, filter-resident and streaming, and with S2S_CONV_STAGE=0 (tests/test_env_variants_gpu.py) the persistent
+    kernel with one channel tile.  A row count that matches neither layout is refused."""
+    from stain2stain_amd import ops
+    B, H, W, cin, cout = case
+    dtype = torch.bfloat16
+    L = ops._L()
+    g = torch.Generator().manual_seed(29)
+    x = torch.rand(B, cin, H, W, generator=g) * 2 - 1
+    w = (torch.rand(cout, cin, 3, 3, generator=g) * 2 - 1) * 0.1
+    xs = nhwc(x, dtype)
+    wf, _ = ops.pack_conv3x3(w.to(DEV), dtype)
+    blocks = L.s2s_conv3x3_stat_blocks(0, B, H, W, cout)
+    assert 0 < L.s2s_conv3x3_stat_rows(0, B, H, W, cout, cin, 0, cin, 8, 0) != blocks
+    y = torch.empty(B, H, W, cout, dtype=dtype, device=DEV)
+    stat = torch.full((2, cout, blocks), float("nan"), device=DEV)
+
+    def launch(rows):
+        return L.s2s_conv3x3_nhwc_s(0, xs.data_ptr(), cin, cin, None, 8, 0, wf.data_ptr(), None, y.data_ptr(), cout,
+                                    stat.data_ptr(), rows, None, None, 0, None, B, H, W, cout, ops._stream())
+
+    assert launch(0) == 0
+    torch.cuda.synchronize()
+    yb = nchw(y)
+    assert relerr(yb, F.conv2d(rnd(x, dtype), rnd(w, dtype), None, padding=1)) < tol_act(dtype)
+    assert not stat.isnan().any()                      # every row of the layout is written
+    s = stat.sum(-1).cpu()
+    assert relerr(s[0], yb.sum((0, 2, 3))) < 2e-4
+    assert relerr(s[1], (yb * yb).sum((0, 2, 3))) < 2e-4
+    assert launch(blocks + 8) == -1
+
+
 @pytest.mark.parametrize("case", [(6, 250, 270, 64, 0, 64), (3, 250, 270, 64, 0, 136), (16, 100, 130, 64, 128, 64),
                                   (6, 250, 270, 8, 0, 64)])
 def test_conv3x3_staged_eval_affine(case):
