@@ -247,6 +247,25 @@ int s2s_pil_resize_bilinear_normalize(const void* src_u8, void* tmp_u8, const in
                                       int ksize_h, const int* bounds_v, const int* kk_v, int ksize_v, void* out_u8,
                                       float* out_f, int B, int Hs, int Ws, int Ho, int Wo, void* stream);
 
+/* ---- tiled whole-region translation (region.hip) -----------------------------------------------------
+ * What runs between two sampler calls of stain2stain_amd.region.translate_region; no atomics, bit-reproducible.
+ * s2s_region_gather: tiles out: float [B][3][T][T] = (u / 255 - 0.5) / 0.5 of a uint8 RGB image (row pitch `pitch`
+ *   bytes, 3 contiguous bytes per pixel) whose buffer holds image rows [band_top, band_top + band_h) of an H x W image;
+ *   origins: int32 [B][2] {top, left}.  Pixels outside the image fold back as numpy.pad(mode="reflect"); T % 4 == 0.
+ * s2s_region_blend: adds tiles [n][c0][T][T] (+ tiles1 [n][c1][T][T], optional) into acc, a ring of band_rows image
+ *   rows of C + 1 = c0 + c1 + 1 interleaved floats per pixel (row r at r % band_rows): C sums of w * v and the sum of
+ *   w, w = wy(i) * wx(j), w(i) = min(1, (i + 0.5) / overlap, (T - i - 0.5) / overlap) (1 when overlap == 0).  Image
+ *   rows [r0, r1) (r1 - r0 <= band_rows) are updated, tiles in the given order, one writer per element.  C <= 8.
+ * s2s_region_finalize: rows [r0, r1): out = acc / wsum; out_f (optional) float [.][W][C] with row pitch pitch_f
+ *   elements, out_u8 (optional, C >= 3) uint8 [.][W][3] of channels 0..2 as trunc(clamp((out * 0.5 + 0.5) * 255,
+ *   0, 255)) with row pitch pitch_u8 bytes; both buffers start at image row out_top.  The ring rows are cleared. */
+int s2s_region_gather(const void* img_u8, long pitch, int H, int W, int band_top, int band_h, const int* origins,
+                      float* out, int B, int T, void* stream);
+int s2s_region_blend(const float* tiles, int c0, const float* tiles1, int c1, const int* origins, int n, int T,
+                     int overlap, float* acc, int band_rows, int H, int W, int r0, int r1, void* stream);
+int s2s_region_finalize(float* acc, int band_rows, int W, int C, int r0, int r1, void* out_u8, long pitch_u8,
+                        float* out_f, long pitch_f, int out_top, void* stream);
+
 /* ---- segmentation loss (seg_loss.hip) -- SURVEY section 8 row f2 --------------------------------------
  * seg = dw * DiceLoss(sigmoid(z), g) + (1-dw) * BCEWithLogits(z, g)  (conditional_flow_matching_multitask.py:36-53,
  * 174-202).  z, g: float[n]; out: float[3] = {seg, dice, bce}; dz (optional) = grad_scale * d seg / dz;

@@ -20,6 +20,7 @@ from .optim import FusedAdam
 from .ema import FusedEMA
 from .multitask_trainer import MultiTaskTrainer
 from .evaluation import EvalAccumulator
+from .region import multitask_sampler, plan_tiles, translate_region
 
 __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeEmbedding", "FlowUNet",
            "ConditionalFlowMatcher", "ConditionalFlowMatchingModule", "MultiTaskFlowMatchingModule", "euler_generate", "dopri5_generate", "euler_integrate", "dopri5_integrate", "SolverConfig", "GraphedVelocity",
@@ -27,4 +28,4 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "MaskConditionedFlowMatchingModule", "ROICharbonnierFlowMatchingModule", "ROIWeightedFlowMatchingModule",
            "checkpoint", "InstanceNormLeakyReLU", "Conv4x4Stride1", "Conv4x4Stride2", "ConvTranspose4x4Stride2",
            "Pix2PixGenerator", "PatchGANDiscriminator", "Pix2PixTrainer", "FusedAdam", "FusedEMA", "MultiTaskTrainer",
-           "EvalAccumulator"]
+           "EvalAccumulator", "plan_tiles", "translate_region", "multitask_sampler"]

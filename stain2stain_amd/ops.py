@@ -1741,3 +1741,75 @@ def convsm_wins(dtype: torch.dtype, mode: int, B: int, h: int, w: int, cin: int,
     if mode == 1:
         return h * w <= 4 or (h * w <= 16 and cout <= 512)
     return h * w <= 4
+
+
+# ------------------------------------------------------------------------------------------------
+# tiled whole-region translation (region.hip; the driver is region.translate_region)
+# ------------------------------------------------------------------------------------------------
+def _u8_rows(img: torch.Tensor) -> Tuple[int, int]:
+    """(data_ptr, row pitch in bytes) of a uint8 [rows, W, 3] GPU view whose pixels are contiguous within a row."""
+    if not img.is_cuda:
+        raise RuntimeError("stain2stain_amd: tensor is not on the GPU (there is no CPU path)")
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+        raise RuntimeError("stain2stain_amd: expected a uint8 [rows, W, 3] image")
+    rows, w, _ = img.shape
+    if img.stride(2) != 1 or (w > 1 and img.stride(1) != 3):
+        raise RuntimeError("stain2stain_amd: image pixels must be contiguous within a row")
+    pitch = img.stride(0) if rows > 1 else 3 * w
+    if pitch < 3 * w:
+        raise RuntimeError("stain2stain_amd: image rows overlap")
+    return img.data_ptr(), pitch
+
+
+def region_gather(band: torch.Tensor, band_top: int, H: int, W: int, origins: torch.Tensor, tile: int,
+                  out: torch.Tensor) -> torch.Tensor:
+    """out[n] = Normalize(0.5, 0.5)(to_tensor(tile at origins[n])), fp32 [B, 3, tile, tile]: ``band`` holds image rows
+    [band_top, band_top + band.shape[0]) of an H x W uint8 RGB image; pixels outside the image fold back by reflection."""
+    ptr, pitch = _u8_rows(band)
+    B = origins.shape[0]
+    if (origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 2 or not origins.is_cuda
+            or not origins.is_contiguous()):
+        raise RuntimeError("stain2stain_amd: region_gather origins must be contiguous int32 [B, 2] on the GPU")
+    if tuple(out.shape) != (B, 3, tile, tile):
+        raise RuntimeError("stain2stain_amd: region_gather output shape mismatch")
+    rc = _L().s2s_region_gather(ptr, pitch, int(H), int(W), int(band_top), int(band.shape[0]), origins.data_ptr(),
+                                _f32(out), int(B), int(tile), _stream())
+    _native.check(rc, "region_gather")
+    return out
+
+
+def region_blend(tiles: torch.Tensor, tiles1: Optional[torch.Tensor], origins: torch.Tensor, overlap: int,
+                 acc: torch.Tensor, band_rows: int, H: int, W: int, r0: int, r1: int) -> None:
+    """acc (+)= the feathered tiles[k] (channels of ``tiles`` then of ``tiles1``) at origins[k], in order, over image
+    rows [r0, r1) of the ring ``acc`` (fp32 [band_rows, W, C + 1])."""
+    n, c0, T = tiles.shape[0], tiles.shape[1], tiles.shape[-1]
+    c1 = 0 if tiles1 is None else tiles1.shape[1]
+    if tiles1 is not None and tuple(tiles1.shape) != (n, c1, T, T):
+        raise RuntimeError("stain2stain_amd: region_blend second operand shape mismatch")
+    if origins.dtype != torch.int32 or tuple(origins.shape) != (n, 2) or not origins.is_contiguous():
+        raise RuntimeError("stain2stain_amd: region_blend origins must be contiguous int32 [n, 2]")
+    if tuple(acc.shape) != (band_rows, W, c0 + c1 + 1):
+        raise RuntimeError("stain2stain_amd: region_blend accumulator shape mismatch")
+    rc = _L().s2s_region_blend(_f32(tiles), int(c0), _f32(tiles1), int(c1), _ptr(origins), int(n), int(T),
+                               int(overlap), _f32(acc), int(band_rows), int(H), int(W), int(r0), int(r1), _stream())
+    _native.check(rc, "region_blend")
+
+
+def region_finalize(acc: torch.Tensor, r0: int, r1: int, out_u8: Optional[torch.Tensor],
+                    out_f: Optional[torch.Tensor], out_top: int) -> None:
+    """Rows [r0, r1) of the ring: out_f[r - out_top] = acc / wsum (fp32 [., W, C]), out_u8[r - out_top] = the uint8
+    save conversion of channels 0..2; the ring rows are cleared."""
+    band_rows, W, C1 = acc.shape
+    pu8, pitch_u8, pf, pitch_f = 0, 0, 0, 0
+    if out_u8 is not None:
+        pu8, pitch_u8 = _u8_rows(out_u8)
+        if out_u8.shape[1] != W or out_u8.shape[0] < r1 - out_top:
+            raise RuntimeError("stain2stain_amd: region_finalize uint8 output too small")
+    if out_f is not None:
+        if (not out_f.is_cuda or out_f.dtype != torch.float32 or out_f.dim() != 3 or tuple(out_f.shape[1:]) != (W, C1 - 1)
+                or out_f.stride(2) != 1 or out_f.stride(1) != C1 - 1 or out_f.shape[0] < r1 - out_top):
+            raise RuntimeError("stain2stain_amd: region_finalize fp32 output must be [rows, W, C] with contiguous rows")
+        pf, pitch_f = out_f.data_ptr(), out_f.stride(0)
+    rc = _L().s2s_region_finalize(_f32(acc), int(band_rows), int(W), int(C1 - 1), int(r0), int(r1), pu8, int(pitch_u8),
+                                  pf, int(pitch_f), int(out_top), _stream())
+    _native.check(rc, "region_finalize")
