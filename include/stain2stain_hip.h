@@ -70,6 +70,13 @@ int s2s_conv3x3_stat_rows(int dtype, int B, int H, int W, int Cout, int c0, int 
  * per filter tap), 1 = conv3x3_stage_kernel streaming its weights per 32-channel chunk, 2 = the same with the filter
  * resident in LDS (<= 64 input channels).  Diagnostic: tests and scripts assert the path they mean to measure. */
 int s2s_conv3x3_staged(int dtype, int B, int H, int W, int Cout, int c0, int c1, int ld0, int ld1, int ldy, int stats);
+/* Diagnostic: the kernel family the launch s2s_conv3x3_nhwc_s makes of these operands (stat_rows as passed to it; kwork
+ * = a split-K workspace is offered, as s2s_conv3x3_nhwc_k with kwork): 0 = conv3x3_stage_kernel with the filter resident,
+ * 1 = the same streaming the filter, 2 = the persistent per-tap kernel carrying statistics per workgroup, 3 = the same
+ * with per-tile statistics or none, 4 = one tile per workgroup (split-K possible), 5 = the fp32 parity kernel; negative:
+ * the launch is refused.  Tests pin the kernel a case was written for with it. */
+int s2s_conv3x3_family(int dtype, int B, int H, int W, int Cout, int c0, int c1, int ld0, int ld1, int ldy, int has_bias,
+                       int has_affine, int stats, int stat_rows, int kwork);
 int s2s_conv3x3_nhwc_s(int dtype, const void* x0, int ld0, int c0, const void* x1, int ld1, int c1, const void* w_packed,
                        const float* bias, void* y, int ldy, float* stat_part, int stat_rows, const float* ep_scale,
                        const float* ep_shift, int relu, float* kwork, int B, int H, int W, int Cout, void* stream);

@@ -1598,7 +1598,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_stage_kernel(Conv3x3Args a, in
   bool pend = false, pend_full = false;                // a packed tile waits in outv / it was a full tile (NST stores)
   bool ynst = false;                                   // exactly NST stores are younger than the newest DMA
   int st = 0;
-  const int by_first = cur.n0 / BN;
+  unsigned long long seen = 0;                         // STATS == 2: channel tiles flushed so far (bit by; GY <= 64)
 
   auto step = [&](int c, auto mayc) {
     constexpr bool MAY_DEFER = decltype(mayc)::value;
@@ -1662,6 +1662,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_stage_kernel(Conv3x3Args a, in
       load_affine(nxt.n0);                             // (pack() of the current tile is done)
       if constexpr (STATS == 2) {                      // (a wave row's sums of this channel tile: written once)
         conv_stats_flush<BN, WN>(a, cs1, cs2, cur.n0, tid, (long)blockIdx.x * WM + wm);
+        seen |= 1ull << (cur.n0 / BN);
         stats_zero();
         ynst = false;
       }
@@ -1680,12 +1681,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_stage_kernel(Conv3x3Args a, in
   if (pend) static_for<NST>([&](auto uc) { store_unit(uc, prv); });
   if constexpr (STATS == 2) {
     conv_stats_flush<BN, WN>(a, cs1, cs2, cur.n0, tid, (long)blockIdx.x * WM + wm);
-    // zero rows for the channel tiles this workgroup never visited: RESIDENT job lists are monotonic in the channel tile;
-    // streaming ones keep ONE channel tile per workgroup (stage_grid() admits statistics only when GY divides 32)
+    // zero rows for the channel tiles this workgroup never flushed.  A RESIDENT walk is monotonic in the channel tile
+    // but need not be contiguous: with fewer pixel tiles than workgroups (GX < G) it can jump over a channel tile between
+    // two it visits, so the visited tiles are tracked (a workgroup-uniform mask), not taken as a range
+    seen |= 1ull << (cur.n0 / BN);
     stats_zero();
-    const int by_last = cur.n0 / BN;
     for (int by = 0; by < GY; ++by) {
-      if (by < by_first || by > by_last) conv_stats_flush<BN, WN>(a, cs1, cs2, by * BN, tid, (long)blockIdx.x * WM + wm);
+      if (!((seen >> by) & 1)) conv_stats_flush<BN, WN>(a, cs1, cs2, by * BN, tid, (long)blockIdx.x * WM + wm);
     }
   }
 }
@@ -1714,6 +1716,7 @@ inline int stage_grid(const Conv3x3Args& a, bool stats, bool split) {
   // statistics are carried per (workgroup, channel tile): the streaming order keeps one channel tile per workgroup only
   // when GY divides the 32 workgroups of an XCD
   if (stats && a.c0 + a.c1 > 64 && (GY > 32 || (32 % GY))) return 0;
+  if (stats && GY > 64) return 0;                      // (the kernel's mask of visited channel tiles has 64 bits)
   return slots;
 }
 
@@ -2607,6 +2610,23 @@ extern "C" int s2s_conv3x3_staged(int dtype, int B, int H, int W, int Cout, int 
   if (dtype != S2S_BF16) return 0;
   const int f = conv3x3_query(dtype, B, H, W, Cout, c0, c1, ld0, ld1, ldy, false, stats != 0, kAnyRows, false).family;
   return f == kStageResident ? 2 : f == kStageStream ? 1 : 0;
+}
+
+extern "C" int s2s_conv3x3_family(int dtype, int B, int H, int W, int Cout, int c0, int c1, int ld0, int ld1, int ldy,
+                                  int has_bias, int has_affine, int stats, int stat_rows, int kwork) {
+  if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || c0 <= 0 || c1 < 0) return S2S_ERR_SHAPE;
+  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  static float present;
+  Conv3x3Args a{};
+  conv3x3_fill_args(a, ld0, c0, ld1, c1, has_bias ? &present : nullptr, B, H, W, Cout);
+  a.ldy = ldy;
+  a.ep_scale = has_affine ? &present : nullptr;
+  a.ep_shift = a.ep_scale;
+  a.stat_part = stats ? &present : nullptr;
+  a.stat_rows_req = stat_rows;
+  a.kpart = kwork ? &present : nullptr;
+  const Conv3x3Plan p = conv3x3_plan(dtype, a);
+  return p.rc != S2S_OK ? p.rc : p.family;
 }
 
 extern "C" int s2s_conv3x3_nhwc_k(int dtype, const void* x0, int ld0, int c0, const void* x1, int ld1, int c1,

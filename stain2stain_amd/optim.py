@@ -72,18 +72,25 @@ class FusedAdam(torch.optim.Optimizer):
                             for p, g, st in items)
                 hit = self._desc_cache.get(gi)
                 if hit is None or hit[0] != key:
+                    # empty parameters (torch.optim.Adam accepts them: their step still advances above) have no blocks
+                    # and no row -- s2s_adam_multi_blocks(0) is an error code, not a count
                     rows, start = [], 0
                     for p, g, st in items:
+                        if p.numel() == 0:
+                            continue
+                        nb = L.s2s_adam_multi_blocks(p.numel())
+                        _native.check(nb if nb < 0 else 0, "adam_multi_blocks")
                         rows.append([p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                                      p.numel(), start])
-                        start += L.s2s_adam_multi_blocks(p.numel())
-                    hit = (key, self._table(rows, dev), start)
+                        start += nb
+                    hit = (key, self._table(rows, dev) if rows else None, start, len(rows))
                     self._desc_cache[gi] = hit
-                with torch.cuda.device(dev):
-                    rc = L.s2s_adam_multi(hit[1].data_ptr(), len(items), int(hit[2]), int(step), float(group["lr"]),
-                                          float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
-                                          float(group["weight_decay"]), 1.0, ops._stream())
-                _native.check(rc, "adam_multi")
+                if hit[3]:
+                    with torch.cuda.device(dev):
+                        rc = L.s2s_adam_multi(hit[1].data_ptr(), hit[3], int(hit[2]), int(step), float(group["lr"]),
+                                              float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
+                                              float(group["weight_decay"]), 1.0, ops._stream())
+                    _native.check(rc, "adam_multi")
                 for p, _, _ in items:          # the kernel wrote through raw pointers: tell torch (packed-weight caches)
                     torch.autograd.graph.increment_version(p)
         engine.mutation_epoch[0] += 1

@@ -46,6 +46,44 @@ def test_fused_adam_matches_torch_adam_and_shares_its_state_dict():
     od.step()
 
 
+def test_fused_adam_with_empty_parameters_matches_torch_adam():
+    """torch.optim.Adam accepts parameters with no elements (their step still advances).  Empty ones at the start, in the
+    middle and at the end of the group must not move the block table of the others."""
+    from stain2stain_amd import FusedAdam
+
+    def params(seed):
+        g = torch.Generator().manual_seed(seed)
+        shapes = [(0,), (64, 3, 3, 3), (5000,), (0, 7), (7,), (256, 256), (0,)]
+        return [torch.randn(s, generator=g).to(DEV).requires_grad_(True) for s in shapes]
+
+    pa, pb = params(3), params(3)
+    oa = FusedAdam(pa, lr=1e-3, weight_decay=1e-2)
+    ob = torch.optim.Adam(pb, lr=1e-3, weight_decay=1e-2, foreach=False)
+    g = torch.Generator().manual_seed(4)
+    for _ in range(3):
+        for a, b in zip(pa, pb):
+            gr = torch.randn(a.shape, generator=g).to(DEV)
+            a.grad, b.grad = gr.clone(), gr.clone()
+        oa.step(); ob.step()
+    for a, b in zip(pa, pb):
+        assert a.shape == b.shape
+        if b.numel():
+            assert float((a.detach() - b.detach()).abs().max() / b.detach().abs().max()) < 2e-6
+    sa, sb = oa.state_dict(), ob.state_dict()
+    assert sorted(sa["state"]) == sorted(sb["state"])
+    for i in sb["state"]:
+        assert float(sa["state"][i]["step"]) == float(sb["state"][i]["step"]) == 3.0
+        assert sa["state"][i]["exp_avg"].shape == sb["state"][i]["exp_avg"].shape
+        if sb["state"][i]["exp_avg"].numel():
+            assert float((sa["state"][i]["exp_avg"] - sb["state"][i]["exp_avg"]).abs().max()) < 1e-6
+            assert float((sa["state"][i]["exp_avg_sq"] - sb["state"][i]["exp_avg_sq"]).abs().max()) < 1e-6
+    only_empty = [torch.zeros(0, device=DEV, requires_grad=True)]   # nothing to launch: no error, the step advances
+    only_empty[0].grad = torch.zeros(0, device=DEV)
+    oe = FusedAdam(only_empty)
+    oe.step()
+    assert float(oe.state[only_empty[0]]["step"]) == 1.0
+
+
 def test_fused_adam_refuses_cpu_parameters():
     from stain2stain_amd import FusedAdam
     p = torch.zeros(4, requires_grad=True)

@@ -130,6 +130,11 @@ STAGE_CASES = [
     (300, 8, 40, 24, 0, 64, False, 1),      # H = 8 < 16, 24 input channels (one partial chunk), W tail
     (5, 120, 130, 128, 0, 192, True, 9),    # ... with statistics: never staged (3 does not divide 32), per-tap kernels
     (1, 64, 64, 128, 0, 128, True, 9),      # few tiles: per-tap kernels
+    # resident statistics with fewer pixel tiles than workgroups (GX < 256): a workgroup's walk jumps over channel tiles
+    (1, 256, 256, 64, 0, 256, True, 1),     # XCD order, GX = 128: workgroups k < 16 visit channel tiles 0 and 2 only
+    (1, 240, 270, 64, 0, 256, True, 1),     # plain order, GX = 135: workgroup 0 visits channel tiles 0, 1 and 3
+    (2, 200, 256, 64, 0, 192, True, 1),     # GY = 3
+    (1, 256, 256, 8, 0, 256, True, 1),      # the stem's 8-channel image
 ]
 
 
@@ -154,6 +159,15 @@ def test_conv3x3_staged_kernel(case):
     if stats and path:                                 # staged: one row per (workgroup, wave row), 256 x 8
         assert ops._L().s2s_conv3x3_stat_rows(0, B, H, W, cout, c0, c1, xs.shape[3], xs.shape[3], 0) == 256 * 8
     y, stat = ops.conv3x3(x0, x1, wf, None, cout, want_stats=stats)
+    if stats:                                          # the same launch into NaN-filled rows: every row is written
+        L = ops._L()
+        rows = L.s2s_conv3x3_stat_rows(0, B, H, W, cout, c0, c1, xs.shape[3], xs.shape[3], 0)
+        stat = torch.full((2, cout, rows), float("nan"), device=DEV)
+        assert L.s2s_conv3x3_nhwc_s(0, x0.data_ptr(), xs.shape[3], c0, x1.data_ptr() if c1 else None, xs.shape[3], c1,
+                                    wf.data_ptr(), None, y.data_ptr(), cout, stat.data_ptr(), rows, None, None, 0, None,
+                                    B, H, W, cout, ops._stream()) == 0
+        torch.cuda.synchronize()
+        assert not stat.isnan().any()
     torch.cuda.synchronize()
     assert relerr(nchw(y), ref) < tol_act(dtype)
     if stats:
