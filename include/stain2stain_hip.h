@@ -194,6 +194,26 @@ int s2s_mse_loss(const float* v, const float* u, float* dv, float grad_scale, fl
 int s2s_ode_error_norm(const float* e, const float* y0, const float* y1, float atol, float rtol, float* out,
                        double* work, long n, void* stream);
 int s2s_axpy(float* x, const float* y, float a, long n, void* stream);
+/* ---- per-sample adaptive Dormand-Prince 5(4) (ode.hip) ---------------------------------------------------------
+ * fp32 NCHW [B, n] tensors, n % 4 == 0, 16-byte aligned; state: double[B * 8] per-sample rows (t, h, accepted,
+ * rejected, last-step-rejected, done, accept mask, aux); status: int[4] (active samples, step limit reached, attempted
+ * steps, 0); part: double[2 * B * s2s_dp_partials(n)].  Nothing allocates or synchronises (capturable).
+ * s2s_dp_init phase 0 (after k1 = v(0, y)): d0, d1, h0, t = 0, out = y + h0 k1, t_out = h0; phase 1 (after
+ * fa = v(h0, out)): the first step h, counters, status.  s2s_dp_stage i = 1..6: out = y + sum_j (h a_ij) k_j,
+ * t_out = float(t + c_i h) (i = 6 is y_new).  s2s_dp_error: per-sample scaled square sums of the error estimate;
+ * s2s_dp_control: norm, accept / reject, t, h, counters, status; s2s_dp_commit: accepted samples y <- y_new, k1 <- k7. */
+int s2s_dp_partials(long n);
+int s2s_dp_init(int phase, const float* y, const float* k1, const float* fa, double* state, double* part, float* out,
+                float* t_out, int* status, float atol, float rtol, int B, long n, void* stream);
+int s2s_dp_stage(int i, const float* y, const float* k1, const float* k2, const float* k3, const float* k4,
+                 const float* k5, const float* k6, const double* state, float* out, float* t_out, int B, long n,
+                 void* stream);
+int s2s_dp_error(const float* k1, const float* k2, const float* k3, const float* k4, const float* k5, const float* k6,
+                 const float* k7, const float* y, const float* y_new, const double* state, double* part, float atol,
+                 float rtol, int B, long n, void* stream);
+int s2s_dp_control(double* state, const double* part, int* status, int max_steps, int B, long n, void* stream);
+int s2s_dp_commit(float* y, const float* y_new, float* k1, const float* k7, const double* state, int B, long n,
+                  void* stream);
 int s2s_fill_f32(float* x, float v, long n, void* stream);
 /* t[0..n) <- table[*counter], then *counter += 1: the time input of a hipGraph-captured Euler step (the captured
  * kernel walks a table of the node times, so a replay needs no host-side argument). */

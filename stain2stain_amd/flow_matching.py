@@ -212,11 +212,17 @@ _DP_E = (-71 / 57600, 0.0, 71 / 16695, -71 / 1920, 17253 / 339200, -22 / 525, 1 
 
 @torch.no_grad()
 def dopri5_generate(net, source_img: torch.Tensor, atol: float = 1e-4, rtol: float = 1e-4, max_steps: int = 1000,
-                    return_stats: bool = False, graph: bool = False):
+                    return_stats: bool = False, graph: bool = False, per_sample: bool = False):
     """``dopri5_integrate`` on a network put in eval mode for the solve (mode restored, also when it raises).
-    ``graph=True``: every stage evaluation is a replay of one captured forward (GraphedVelocity)."""
+    ``graph=True``: every stage evaluation is a replay of one captured forward (GraphedVelocity); with
+    ``per_sample=True`` one whole attempted step (6 stage kernels, 6 evaluations, error, control, commit) is one replayed
+    capture, cached on the network like the Euler graph (``net._s2s_dopri5_graph``)."""
     with _eval_mode(net):
         x = _prep_source(source_img)
+        if per_sample:
+            if not graph:
+                return dopri5_integrate(net, x, atol, rtol, max_steps, return_stats, per_sample=True)
+            return _cached_dopri5_graph(net, x, atol, rtol, max_steps).solve(x, return_stats)
         if not graph:
             return dopri5_integrate(net, x, atol, rtol, max_steps, return_stats)
         gv = GraphedVelocity(net, x, None)
@@ -228,7 +234,7 @@ def dopri5_generate(net, source_img: torch.Tensor, atol: float = 1e-4, rtol: flo
 
 @torch.no_grad()
 def dopri5_integrate(net, y: torch.Tensor, atol: float = 1e-4, rtol: float = 1e-4, max_steps: int = 1000,
-                     return_stats: bool = False):
+                     return_stats: bool = False, per_sample: bool = False):
     """Adaptive sampler for a callable ``net(t[B], x)``: x(1) of dx/dt = v(t, x), x(0) = source, eval-mode network, by the Dormand-Prince 5(4) pair.
 
     The reference integrates with torchdyn's ``NeuralODE(solver="dopri5", atol=1e-4, rtol=1e-4)``
@@ -236,7 +242,14 @@ def dopri5_integrate(net, y: torch.Tensor, atol: float = 1e-4, rtol: float = 1e-
     (the same as scipy's ``RK45``: scaled RMS error, factor 0.9 err^(-1/5) clamped to [0.2, 10], no growth right
     after a rejection, Hairer's initial-step heuristic) -- parity with torchdyn's controller is unpinned, the
     solution agrees with any dopri5 to the tolerances.  Stage combinations and the error norm run in HIP
-    (``s2s_axpy``, ``s2s_ode_error_norm``); one host read of the error norm per attempted step."""
+    (``s2s_axpy``, ``s2s_ode_error_norm``); one host read of the error norm per attempted step.
+
+    The error norm, ``t`` and ``h`` are shared by the whole batch, so a sample's result depends on its batch mates.
+    ``per_sample=True`` steps every sample as if it were alone in a batch of one (its own norm, initial step, ``t`` and
+    ``h``, all on the device: ``_PerSampleDopri5``); a sample that reaches t = 1 is frozen until the batch is done.  Its
+    stats are per-sample ``accepted`` / ``rejected`` lists plus ``attempted``, ``evaluations`` and ``host_reads``."""
+    if per_sample:
+        return _PerSampleDopri5(net, y, atol, rtol, max_steps).solve(y, return_stats)
     B = y.shape[0]
 
     def f(t, x):
@@ -295,6 +308,149 @@ def dopri5_integrate(net, y: torch.Tensor, atol: float = 1e-4, rtol: float = 1e-
     return (y, {"accepted": n_acc, "rejected": n_rej}) if return_stats else y
 
 
+class _PerSampleDopri5:
+    """The per-sample Dormand-Prince solver (csrc/ode.hip): device-resident per-sample state
+    (fp64 t, h, counters, flags), fused stage / error / control / commit kernels and every workspace they need.
+
+    One attempted step is ``step()``: stage kernels 1..6 each followed by a network evaluation (the last stage is y_new),
+    the error partials, the controller and the commit; nothing in it allocates outside the network or synchronises, so
+    ``_Dopri5Graph`` captures it whole.  The host reads the 16-byte status word once per attempted step (a non-blocking
+    copy into pinned memory and an event), and the per-sample state once at the end."""
+
+    def __init__(self, net, x_like: torch.Tensor, atol: float, rtol: float, max_steps: int):
+        if not x_like.is_cuda:
+            raise RuntimeError("stain2stain_amd: the per-sample dopri5 solver needs GPU tensors (there is no CPU path)")
+        if x_like.dtype != torch.float32 or x_like.numel() == 0 or (x_like[0].numel() % 4):
+            raise RuntimeError("stain2stain_amd: per-sample dopri5 wants fp32 samples of a multiple of 4 elements")
+        dev, B = x_like.device, x_like.shape[0]
+        self.net, self.atol, self.rtol, self.max_steps = net, float(atol), float(rtol), int(max_steps)
+        self.B, self.n = B, x_like[0].numel()
+        e = lambda: torch.empty_like(x_like, memory_format=torch.contiguous_format)
+        self.y, self.k1, self.xs, self.y_new = e(), e(), e(), e()
+        self.t = torch.empty((B,), dtype=torch.float32, device=dev)
+        self.state = torch.empty((B, 8), dtype=torch.float64, device=dev)
+        self.part = torch.empty((2 * B * ops.dp_partials(self.n),), dtype=torch.float64, device=dev)
+        self.status = torch.empty((4,), dtype=torch.int32, device=dev)
+        self.status_host = torch.empty((4,), dtype=torch.int32, pin_memory=True)
+        self.state_host = torch.empty((B, 8), dtype=torch.float64, pin_memory=True)
+        self.event = torch.cuda.Event()
+        self.host_reads = 0
+
+    def f(self, x: torch.Tensor) -> torch.Tensor:
+        return self.net(self.t, x).contiguous()
+
+    def init(self, source: torch.Tensor) -> None:
+        """y = source, k1 = v(0, y), Hairer's initial step per sample (two evaluations)."""
+        self.y.copy_(source)
+        self.t.zero_()
+        self.k1.copy_(self.f(self.y))
+        ops.dp_init_(0, self.y, self.k1, None, self.state, self.part, self.xs, self.t, self.status, self.atol, self.rtol)
+        fa = self.f(self.xs)
+        ops.dp_init_(1, self.y, self.k1, fa, self.state, self.part, self.xs, self.t, self.status, self.atol, self.rtol)
+
+    def step(self):
+        """One attempted step of every sample; returns k1..k7 (k2..k7 the network's own outputs)."""
+        ks = [self.k1]
+        for i in range(1, 7):
+            out = self.y_new if i == 6 else self.xs
+            ops.dp_stage_(i, self.y, ks, self.state, out, self.t)
+            ks.append(self.f(out))
+        ops.dp_error_(ks, self.y, self.y_new, self.state, self.part, self.atol, self.rtol)
+        ops.dp_control_(self.state, self.part, self.status, min(self.max_steps, 2 ** 31 - 1), self.B, self.n)
+        ops.dp_commit_(self.y, self.y_new, self.k1, ks[6], self.state)
+        return ks
+
+    def _read(self, dev: torch.Tensor, host: torch.Tensor) -> torch.Tensor:
+        host.copy_(dev, non_blocking=True)
+        self.event.record()
+        self.event.synchronize()
+        self.host_reads += 1
+        return host
+
+    def solve(self, source: torch.Tensor, return_stats: bool, replay=None):
+        if self.max_steps < 1:
+            raise RuntimeError("dopri5_generate: max_steps reached before t = 1")
+        self.host_reads = 0
+        self.init(source)
+        attempted = 0
+        while True:
+            if replay is None:
+                self.step()
+            else:
+                replay()
+            attempted += 1
+            active, limit = self._read(self.status, self.status_host).tolist()[:2]
+            if limit:
+                raise RuntimeError("dopri5_generate: max_steps reached before t = 1")
+            if active == 0:
+                break
+        y = self.y if replay is None else self.y.clone()
+        if not return_stats:
+            return y
+        st = self._read(self.state, self.state_host)
+        return y, {"accepted": [int(v) for v in st[:, 2].tolist()], "rejected": [int(v) for v in st[:, 3].tolist()],
+                   "attempted": attempted, "evaluations": 2 + 6 * attempted, "host_reads": self.host_reads}
+
+
+class _Dopri5Graph:
+    """One attempted step of ``_PerSampleDopri5`` captured as a hipGraph on one stream (no forked branches): the stage
+    inputs, y_new, k1 and the state live in the solver's buffers; k2..k7 are the network outputs the capture allocated,
+    read in place.  Cached on the network as ``net._s2s_dopri5_graph`` until the batch shape, the tolerances, the step
+    limit, the parameters or ``engine.mutation_epoch`` change; ``close()`` releases it."""
+
+    def __init__(self, net, x_like: torch.Tensor, atol: float, rtol: float, max_steps: int):
+        self.net = net
+        self.key = self._key(net, x_like, atol, rtol, max_steps)
+        self.solver = s = _PerSampleDopri5(net, x_like, atol, rtol, max_steps)
+        s.t.zero_()
+        s.xs.copy_(x_like)
+        side = torch.cuda.Stream(device=x_like.device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                   # warm-up: packed weights, folded BN constants, LDS attributes
+            for _ in range(2):
+                net(s.t, s.xs)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with ops.capture_graph(self.graph):
+            self.ks = s.step()
+
+    @staticmethod
+    def _key(net, x, atol, rtol, max_steps):
+        from . import engine
+        return (tuple(x.shape), float(atol), float(rtol), int(max_steps), engine.mutation_epoch[0],
+                tuple(p._version for p in _params(net)))
+
+    def matches(self, net, x, atol, rtol, max_steps) -> bool:
+        return self.graph is not None and net is self.net and self.key == self._key(net, x, atol, rtol, max_steps)
+
+    def solve(self, source: torch.Tensor, return_stats: bool = False):
+        return self.solver.solve(source, return_stats, replay=self.graph.replay)
+
+    def close(self) -> None:
+        """Release the graph and its private pool now (it sits in a cycle with its network)."""
+        self.graph = None
+        self.ks = None
+        if getattr(self.net, "_s2s_dopri5_graph", None) is self:
+            try:
+                object.__delattr__(self.net, "_s2s_dopri5_graph")
+            except Exception:  # noqa: BLE001
+                pass
+
+
+def _cached_dopri5_graph(net, x: torch.Tensor, atol: float, rtol: float, max_steps: int) -> _Dopri5Graph:
+    g = getattr(net, "_s2s_dopri5_graph", None)
+    if g is None or not g.matches(net, x, atol, rtol, max_steps):
+        if g is not None:
+            g.close()
+        g = _Dopri5Graph(net, x, atol, rtol, max_steps)
+        try:
+            object.__setattr__(net, "_s2s_dopri5_graph", g)    # a plain attribute, not a registered sub-module
+        except Exception:  # noqa: BLE001 -- a callable that takes no attributes: rebuild next time
+            pass
+    return g
+
+
 class SolverConfig:
     """Stand-in for the reference's ``solver:`` entry (a partial of torchdyn's ``NeuralODE``,
     configs/model/conditional_flow_matching.yaml:32-38): the attributes ``generate`` reads from it."""
@@ -315,11 +471,12 @@ def _solver_setting(solver, name: str, default):
 
 
 def _solve(module, f, source_img: torch.Tensor, num_steps: int, method: Optional[str], atol: Optional[float],
-           rtol: Optional[float], graph: bool = False) -> torch.Tensor:
+           rtol: Optional[float], graph: bool = False, per_sample: bool = False) -> torch.Tensor:
     """The ODE solve shared by every ``generate``: like the reference it refuses to run without a solver, puts the
     module in eval mode and LEAVES it there (``self.eval()``, conditional_flow_matching.py:147-150), integrates with
     the solver's method / tolerances (dopri5, 1e-4 when it names none) and returns the end point x(1).  ``method``
-    overrides the solver's choice: "euler" is the ``num_steps`` fixed-step solve of BASELINE.json configs[3]."""
+    overrides the solver's choice: "euler" is the ``num_steps`` fixed-step solve of BASELINE.json configs[3].
+    ``per_sample=True`` (dopri5 only): every sample gets its own step size, so it does not depend on its batch mates."""
     if module.solver is None:
         raise ValueError("Solver is not initialized. Cannot perform inference.")
     module.eval()
@@ -328,10 +485,20 @@ def _solve(module, f, source_img: torch.Tensor, num_steps: int, method: Optional
     rtol = _solver_setting(module.solver, "rtol", 1e-4) if rtol is None else rtol
     x = _prep_source(source_img)
     if method == "dopri5":
+        if per_sample:
+            if not graph:
+                return dopri5_integrate(f, x, atol, rtol, per_sample=True)
+            g = _Dopri5Graph(f, x, atol, rtol, 1000)
+            try:
+                return g.solve(x)
+            finally:
+                g.close()
         if graph:           # every stage evaluation = one replay of the captured forward
             gv = GraphedVelocity(f, x, None)
             return dopri5_integrate(lambda t, y: gv(t, y).clone(), x, atol, rtol)
         return dopri5_integrate(f, x, atol, rtol)
+    if per_sample:
+        raise ValueError("per_sample=True needs the dopri5 solver")
     if method == "euler":
         if graph:
             return GraphedVelocity(f, x, 1.0 / num_steps).solve_euler(x, num_steps)
@@ -381,14 +548,16 @@ class ConditionalFlowMatchingModule(_Base):
 
     @torch.no_grad()
     def generate(self, source_img: torch.Tensor, num_steps: int = 100, method: Optional[str] = None,
-                 atol: Optional[float] = None, rtol: Optional[float] = None, graph: bool = False) -> torch.Tensor:
+                 atol: Optional[float] = None, rtol: Optional[float] = None, graph: bool = False,
+                 per_sample: bool = False) -> torch.Tensor:
         """x(1) of dx/dt = net(t, x), x(0) = source (conditional_flow_matching.py:133-170): the solver's method --
         adaptive dopri5 at atol = rtol = 1e-4 unless ``self.solver`` says otherwise; ``num_steps`` only defined the
         reference's output grid and plays no role for the end point -- or, with ``method="euler"``, ``num_steps``
         fixed Euler steps.  Raises without a solver and leaves the module in eval mode, as the reference does.
         ``graph=True`` replays the network evaluation as a captured hipGraph (the reference samples one tile at a time,
-        infer_simple_flowmatching.py:73-83, where the eager path is launch-bound)."""
-        return _solve(self, self.net, source_img, num_steps, method, atol, rtol, graph)
+        infer_simple_flowmatching.py:73-83, where the eager path is launch-bound).  ``per_sample=True``: dopri5 with a
+        step size per sample (``dopri5_integrate``), each result independent of its batch mates."""
+        return _solve(self, self.net, source_img, num_steps, method, atol, rtol, graph, per_sample)
 
 
 class _WeightedMSE(torch.autograd.Function):
@@ -459,11 +628,13 @@ class MaskConditionedFlowMatchingModule(ConditionalFlowMatchingModule):
 
     @torch.no_grad()
     def generate(self, source_img: torch.Tensor, mask: torch.Tensor, num_steps: int = 100,
-                 method: Optional[str] = None, atol: Optional[float] = None, rtol: Optional[float] = None) -> torch.Tensor:
+                 method: Optional[str] = None, atol: Optional[float] = None, rtol: Optional[float] = None,
+                 per_sample: bool = False) -> torch.Tensor:
         """conditional_flow_matching_conditional_mask.py:143-199: the mask rides along as a constant fourth channel."""
         if source_img.dim() == 3:
             source_img, mask = source_img.unsqueeze(0), mask.unsqueeze(0)
-        return _solve(self, lambda t, x: self.forward(t, x, mask), source_img, num_steps, method, atol, rtol)
+        return _solve(self, lambda t, x: self.forward(t, x, mask), source_img, num_steps, method, atol, rtol,
+                      per_sample=per_sample)
 
 
 class ClassConditionalFlowMatchingModule(ConditionalFlowMatchingModule):
@@ -480,7 +651,7 @@ class ClassConditionalFlowMatchingModule(ConditionalFlowMatchingModule):
 
     @torch.no_grad()
     def generate(self, source_img: torch.Tensor, target_class, num_steps: int = 100, method: Optional[str] = None,
-                 atol: Optional[float] = None, rtol: Optional[float] = None) -> torch.Tensor:
+                 atol: Optional[float] = None, rtol: Optional[float] = None, per_sample: bool = False) -> torch.Tensor:
         """class_conditional_flow_matching.py:130-190: ``target_class`` an int or a [B] tensor."""
         if source_img.dim() == 3:
             source_img = source_img.unsqueeze(0)
@@ -491,7 +662,7 @@ class ClassConditionalFlowMatchingModule(ConditionalFlowMatchingModule):
         def f(t, x):
             return self.net(t, x, y=(y.expand(x.shape[0]) if y.dim() == 0 else y[:x.shape[0]]))
 
-        return _solve(self, f, source_img, num_steps, method, atol, rtol)
+        return _solve(self, f, source_img, num_steps, method, atol, rtol, per_sample=per_sample)
 
 
 class _SegLoss(torch.autograd.Function):
@@ -635,7 +806,7 @@ class MultiTaskFlowMatchingModule(_Base):
 
     @torch.no_grad()
     def generate(self, source_img: torch.Tensor, num_steps: int = 100, method: Optional[str] = None,
-                 atol: Optional[float] = None, rtol: Optional[float] = None):
+                 atol: Optional[float] = None, rtol: Optional[float] = None, per_sample: bool = False):
         """(generated image, mask probabilities / class map) like the reference's generate (:419-484): the module goes
         to eval mode and stays there, the mask head runs once on the source, the flow is integrated with the solver's
         method (dopri5 at 1e-4 by default; ``method="euler"`` = ``num_steps`` fixed steps)."""
@@ -649,4 +820,5 @@ class MultiTaskFlowMatchingModule(_Base):
             pred_mask = torch.argmax(torch.softmax(logits, dim=1), dim=1, keepdim=True)
         else:
             pred_mask = torch.sigmoid(logits)
-        return _solve(self, self.forward_flow, source_img, num_steps, method, atol, rtol), pred_mask
+        return (_solve(self, self.forward_flow, source_img, num_steps, method, atol, rtol, per_sample=per_sample),
+                pred_mask)

@@ -866,6 +866,55 @@ def axpy_(x: torch.Tensor, y: torch.Tensor, a: float) -> None:
     _native.check(_L().s2s_axpy(_f32(x), _f32(y), float(a), x.numel(), _stream()), "axpy")
 
 
+# per-sample Dormand-Prince (ode.hip): y, k_j, out fp32 [B, ...]; state float64 [B, 8]; part float64
+# [2 * B * dp_partials(n)]; status int32 [4]; t_out float32 [B].  See include/stain2stain_hip.h.
+def dp_partials(n: int) -> int:
+    return int(_L().s2s_dp_partials(int(n)))
+
+
+def _f64(t: torch.Tensor) -> int:
+    if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+        raise RuntimeError("stain2stain_amd: expected a contiguous float64 GPU tensor")
+    return t.data_ptr()
+
+
+def _i32(t: torch.Tensor) -> int:
+    if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
+        raise RuntimeError("stain2stain_amd: expected a contiguous int32 GPU tensor")
+    return t.data_ptr()
+
+
+def dp_init_(phase: int, y, k1, fa, state, part, out, t_out, status, atol: float, rtol: float) -> None:
+    B = y.shape[0]
+    _native.check(_L().s2s_dp_init(int(phase), _f32(y), _f32(k1), _f32(fa), _f64(state), _f64(part), _f32(out),
+                                   _f32(t_out), _i32(status), float(atol), float(rtol), B, y.numel() // B, _stream()),
+                  "dp_init")
+
+
+def dp_stage_(i: int, y, ks, state, out, t_out) -> None:
+    B = y.shape[0]
+    kp = [_f32(k) for k in ks[:i]] + [0] * (6 - i)
+    _native.check(_L().s2s_dp_stage(int(i), _f32(y), *kp, _f64(state), _f32(out), _f32(t_out), B, y.numel() // B,
+                                    _stream()), "dp_stage")
+
+
+def dp_error_(ks, y, y_new, state, part, atol: float, rtol: float) -> None:
+    B = y.shape[0]
+    _native.check(_L().s2s_dp_error(*[_f32(k) for k in ks], _f32(y), _f32(y_new), _f64(state), _f64(part), float(atol),
+                                    float(rtol), B, y.numel() // B, _stream()), "dp_error")
+
+
+def dp_control_(state, part, status, max_steps: int, B: int, n: int) -> None:
+    _native.check(_L().s2s_dp_control(_f64(state), _f64(part), _i32(status), int(max_steps), B, n, _stream()),
+                  "dp_control")
+
+
+def dp_commit_(y, y_new, k1, k7, state) -> None:
+    B = y.shape[0]
+    _native.check(_L().s2s_dp_commit(_f32(y), _f32(y_new), _f32(k1), _f32(k7), _f64(state), B, y.numel() // B,
+                                     _stream()), "dp_commit")
+
+
 def euler_tick_(t: torch.Tensor, table: torch.Tensor, counter: torch.Tensor) -> None:
     """t[:] = table[counter]; counter += 1 (device side; see s2s_euler_tick)."""
     if counter.dtype != torch.int32 or table.dtype != torch.float32:

@@ -74,13 +74,16 @@ def translate_region(image: torch.Tensor, sampler: Callable, *, tile: int = 256,
     a copy), pixels contiguous within a row.  ``sampler``: called with fp32 [batch, 3, tile, tile] on the GPU (the
     normalised tiles, ``(u / 255 - 0.5) / 0.5``); returns fp32 [batch, 3, tile, tile] or a tuple (image, probabilities
     [batch, Cm, tile, tile]) with Cm <= 5.  For a ``FlowUNet``: ``lambda x: euler_generate(net, x, 50, graph=True)``;
-    for ``MultiTaskFlowMatchingModule``: ``multitask_sampler(module, 50)``.
+    for ``MultiTaskFlowMatchingModule``: ``multitask_sampler(module, 50)``.  The reference's adaptive solver, one step size
+    per tile: ``lambda x: dopri5_generate(net, x, per_sample=True, graph=True)`` or
+    ``multitask_sampler(module, 1, method="dopri5")``.
 
     Every sampler call gets exactly ``batch`` tiles (a short last batch is padded by repeating its last tile, the padded
     outputs are discarded), so a captured-graph sampler is captured once per region.  The tile outputs are weighted by
     a separable window ramping over ``overlap`` pixels at every tile edge and normalised by the weight sum; with a
-    fixed-step (Euler) sampler each tile's result is independent of its batch mates, with dopri5 it is not (its step
-    control uses one error norm over the whole batch).
+    fixed-step (Euler) sampler or per-sample dopri5 (``per_sample=True``) each tile's result is independent of its
+    batch mates; with the batch-wide dopri5 (the default ``per_sample=False``) it is not (its step control uses one
+    error norm over the whole batch).
 
     Returns the uint8 [H, W, 3] region on the input's device (the reference's save conversion of the blended image,
     ``trunc(clamp((x * 0.5 + 0.5) * 255, 0, 255))``).  With a tuple-returning sampler the result is a tuple that also
@@ -202,15 +205,21 @@ def translate_region(image: torch.Tensor, sampler: Callable, *, tile: int = 256,
 translate_region.last_stats: Optional[Dict[str, int]] = None
 
 
-def multitask_sampler(module, num_steps: int, graph: bool = True) -> Callable:
+def multitask_sampler(module, num_steps: int, graph: bool = True, *, method: str = "euler", atol: float = 1e-4,
+                      rtol: float = 1e-4) -> Callable:
     """Sampler for ``translate_region`` from a ``MultiTaskFlowMatchingModule``: (the ``num_steps``-step Euler image,
     the mask head's probabilities on the source tiles -- sigmoid(logits) for the binary head, softmax(logits) over the
     classes for the multiclass one).  Class maps cannot be blended; take the argmax of the blended probabilities.
     ``graph``: one captured Euler step replayed ``num_steps`` times, captured once per batch shape (and again after the
-    module's parameters change).  The module is put in eval mode, as its ``generate`` does."""
+    module's parameters change).  The module is put in eval mode, as its ``generate`` does.
+    ``method="dopri5"``: the reference's adaptive solver at ``atol`` / ``rtol`` instead, with a step size per tile
+    (``dopri5_integrate(..., per_sample=True)``), so every tile is independent of its batch mates; ``graph`` then
+    captures one whole attempted step; ``num_steps`` plays no role."""
     from . import engine
-    from .flow_matching import GraphedVelocity, _prep_source, euler_integrate
+    from .flow_matching import GraphedVelocity, _Dopri5Graph, _prep_source, dopri5_integrate, euler_integrate
     num_steps = operator.index(num_steps)
+    if method not in ("euler", "dopri5"):
+        raise ValueError(f"method must be 'euler' or 'dopri5', got {method!r}")
     if num_steps < 1:
         raise ValueError(f"num_steps must be >= 1, got {num_steps}")
     flow = module.forward_flow                            # one bound method: the graph's key
@@ -220,13 +229,18 @@ def multitask_sampler(module, num_steps: int, graph: bool = True) -> Callable:
         module.eval()
         logits = module.forward_segmentation(x)
         probs = torch.softmax(logits, dim=1) if module.num_classes is not None else torch.sigmoid(logits)
+        if method == "dopri5" and not graph:
+            return dopri5_integrate(flow, _prep_source(x), atol, rtol, per_sample=True), probs.float()
         if not graph:
             return euler_integrate(flow, _prep_source(x), num_steps), probs.float()
         key = (tuple(x.shape), engine.mutation_epoch[0], tuple(p._version for p in module.parameters()))
         if state["gv"] is None or state["key"] != key:
             if state["gv"] is not None:
                 state["gv"].close()
-            state["gv"], state["key"] = GraphedVelocity(flow, _prep_source(x), 1.0 / num_steps), key
+            state["gv"], state["key"] = (_Dopri5Graph(flow, _prep_source(x), atol, rtol, 1000) if method == "dopri5"
+                                         else GraphedVelocity(flow, _prep_source(x), 1.0 / num_steps)), key
+        if method == "dopri5":
+            return state["gv"].solve(_prep_source(x)), probs.float()
         return state["gv"].solve_euler(_prep_source(x), num_steps), probs.float()
 
     return sample
