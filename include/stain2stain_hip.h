@@ -214,6 +214,20 @@ int s2s_dp_error(const float* k1, const float* k2, const float* k3, const float*
 int s2s_dp_control(double* state, const double* part, int* status, int max_steps, int B, long n, void* stream);
 int s2s_dp_commit(float* y, const float* y_new, float* k1, const float* k7, const double* state, int B, long n,
                   void* stream);
+/* ---- fixed-step explicit Runge-Kutta schemes with at most four stages (ode.hip) ------------------------------------
+ * fp32 NCHW [B, n] tensors, n % 4 == 0, 16-byte aligned; table: float[table_len] node times, entry step * stages + i
+ * the time of stage i of that step; counter: int[1], the current step.  Nothing allocates or synchronises (capturable).
+ * s2s_rk_stage: out = x + sum_{j<nk} c_j k_j, each term acc = fma(c_j, k_j, acc) from acc = x in argument order (the
+ * rounding of a copy of x followed by one s2s_axpy per term; the caller leaves zero coefficients out and passes
+ * c_j = float(h a_ij)), and t_out[0..B) = table[counter * stages + stage].  out may be NULL when nk = 0: the launch
+ * then writes the node time alone (the first stage evaluates on x itself).  s2s_rk_combine: x += sum_{j<nk} c_j k_j in
+ * place, the same chain with c_j = float(h b_j), nk = 1..4, then counter += 1 from one thread (the only writer of the
+ * counter; the stage kernel only reads it). */
+int s2s_rk_stage(const float* x, const float* k1, const float* k2, const float* k3, float c1, float c2, float c3, int nk,
+                 float* out, float* t_out, const float* table, const int* counter, int stages, int stage, int table_len,
+                 int B, long n, void* stream);
+int s2s_rk_combine(float* x, const float* k1, const float* k2, const float* k3, const float* k4, float c1, float c2,
+                   float c3, float c4, int nk, int* counter, int B, long n, void* stream);
 int s2s_fill_f32(float* x, float v, long n, void* stream);
 /* t[0..n) <- table[*counter], then *counter += 1: the time input of a hipGraph-captured Euler step (the captured
  * kernel walks a table of the node times, so a replay needs no host-side argument). */

@@ -10,7 +10,8 @@ from .flow_matching import (ClassConditionalFlowMatchingModule, ConditionalFlowM
                             ConditionalFlowMatchingModule, MaskConditionedFlowMatchingModule,
                             MultiTaskFlowMatchingModule, ROICharbonnierFlowMatchingModule,
                             GraphedVelocity, ROIWeightedFlowMatchingModule, SolverConfig, dopri5_generate, dopri5_integrate,
-                            euler_generate, euler_integrate)
+                            euler_generate, euler_integrate, FIXED_STEP_METHODS, fixed_step_generate,
+                            fixed_step_integrate)
 from . import checkpoint
 from .pix2pix import (Conv4x4Stride1, Conv4x4Stride2, ConvTranspose4x4Stride2, InstanceNormLeakyReLU,
                       PatchGANDiscriminator, Pix2PixGenerator)
@@ -28,4 +29,5 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "MaskConditionedFlowMatchingModule", "ROICharbonnierFlowMatchingModule", "ROIWeightedFlowMatchingModule",
            "checkpoint", "InstanceNormLeakyReLU", "Conv4x4Stride1", "Conv4x4Stride2", "ConvTranspose4x4Stride2",
            "Pix2PixGenerator", "PatchGANDiscriminator", "Pix2PixTrainer", "FusedAdam", "FusedEMA", "MultiTaskTrainer",
-           "EvalAccumulator", "plan_tiles", "translate_region", "multitask_sampler"]
+           "EvalAccumulator", "plan_tiles", "translate_region", "multitask_sampler", "FIXED_STEP_METHODS",
+           "fixed_step_generate", "fixed_step_integrate"]

@@ -13,6 +13,12 @@
 // coefficients skipped; the error from 0 the same way), so a sample alone in a batch of one is stepped exactly as
 // dopri5_integrate steps it.  The scalar double arithmetic is written with contraction off, as Python evaluates it.
 // Nothing here allocates or synchronises: a whole attempted step can be captured.
+//
+// Fixed-step explicit Runge-Kutta schemes with at most four stages, same conventions:
+//
+//   s2s_rk_stage      out = x + sum_j c_j k_j (c_j = the host's float(h a_ij), zero terms left out) and the node time
+//                     t_out[0..B) = table[counter * stages + stage], one pass
+//   s2s_rk_combine    x += sum_j c_j k_j (c_j = float(h b_j)) in place, one pass; advances the step counter
 #include "common.h"
 
 namespace {
@@ -271,6 +277,67 @@ __global__ __launch_bounds__(kThreads) void dp_commit_kernel(f32x4* __restrict__
   }
 }
 
+// ---- fixed-step explicit Runge-Kutta ------------------------------------------------------------------------------
+// One term of the s2s_axpy chain, x = fma(c, k, x) per element, written as an fma so that no contraction setting can
+// regroup the chain; the results are bit-equal to clone + s2s_axpy per coefficient.
+__device__ __forceinline__ f32x4 rk_term(float c, f32x4 k, f32x4 acc) {
+  const f32x4 c4 = {c, c, c, c};
+  return __builtin_elementwise_fma(c4, k, acc);
+}
+
+// the node time of stage `stage` of step *counter; a step past the table's end reads nothing and yields NaN
+__device__ __forceinline__ float rk_node_time(const float* __restrict__ table, const int* __restrict__ counter, int stages,
+                                              int stage, int table_len) {
+  const long idx = (long)counter[0] * stages + stage;
+  return (idx >= 0 && idx < table_len) ? table[idx] : __builtin_nanf("");
+}
+
+// out = x + sum_{j<NK} c_j k_j, grid (x, B); block (0, b) writes t_out[b].  The counter is only read here.
+template <int NK>
+__global__ __launch_bounds__(kThreads) void rk_stage_kernel(const f32x4* __restrict__ x, const f32x4* __restrict__ k0,
+                                                            const f32x4* __restrict__ k1, const f32x4* __restrict__ k2,
+                                                            float c0, float c1, float c2, f32x4* __restrict__ out,
+                                                            float* __restrict__ t_out, const float* __restrict__ table,
+                                                            const int* __restrict__ counter, int stages, int stage,
+                                                            int table_len, long n4) {
+  const int b = blockIdx.y;
+  if (blockIdx.x == 0 && threadIdx.x == 0) t_out[b] = rk_node_time(table, counter, stages, stage, table_len);
+  const long base = (long)b * n4;
+  for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (long)gridDim.x * kThreads) {
+    f32x4 acc = x[base + i];
+    if (NK > 0) acc = rk_term(c0, k0[base + i], acc);
+    if (NK > 1) acc = rk_term(c1, k1[base + i], acc);
+    if (NK > 2) acc = rk_term(c2, k2[base + i], acc);
+    out[base + i] = acc;
+  }
+}
+
+// the node time alone (the first stage evaluates the network on x itself): t_out[0..B)
+__global__ __launch_bounds__(kThreads) void rk_time_kernel(float* __restrict__ t_out, int B, const float* __restrict__ table,
+                                                           const int* __restrict__ counter, int stages, int stage,
+                                                           int table_len) {
+  const float v = rk_node_time(table, counter, stages, stage, table_len);
+  for (int b = threadIdx.x; b < B; b += kThreads) t_out[b] = v;
+}
+
+// x += sum_{j<NK} c_j k_j in place, grid (x, B); one thread of the launch advances the step counter, nobody reads it
+template <int NK>
+__global__ __launch_bounds__(kThreads) void rk_combine_kernel(f32x4* __restrict__ x, const f32x4* __restrict__ k0,
+                                                              const f32x4* __restrict__ k1, const f32x4* __restrict__ k2,
+                                                              const f32x4* __restrict__ k3, float c0, float c1, float c2,
+                                                              float c3, int* __restrict__ counter, long n4) {
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) counter[0] += 1;
+  const long base = (long)blockIdx.y * n4;
+  for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (long)gridDim.x * kThreads) {
+    f32x4 acc = x[base + i];
+    acc = rk_term(c0, k0[base + i], acc);
+    if (NK > 1) acc = rk_term(c1, k1[base + i], acc);
+    if (NK > 2) acc = rk_term(c2, k2[base + i], acc);
+    if (NK > 3) acc = rk_term(c3, k3[base + i], acc);
+    x[base + i] = acc;
+  }
+}
+
 inline bool misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
 
 inline int check_bn(int B, long n) {
@@ -378,6 +445,75 @@ extern "C" int s2s_dp_commit(float* y, const float* y_new, float* k1, const floa
   const long n4 = n / 4;
   hipLaunchKernelGGL(dp_commit_kernel, dim3(dp_grid_x(n4), B), dim3(kThreads), 0, (hipStream_t)stream, (f32x4*)y,
                      (const f32x4*)y_new, (f32x4*)k1, (const f32x4*)k7, state, n4);
+  S2S_LAUNCH_CHECK();
+  return S2S_OK;
+}
+
+// ---- fixed-step explicit Runge-Kutta ------------------------------------------------------------------------------
+extern "C" int s2s_rk_stage(const float* x, const float* k1, const float* k2, const float* k3, float c1, float c2,
+                            float c3, int nk, float* out, float* t_out, const float* table, const int* counter,
+                            int stages, int stage, int table_len, int B, long n, void* stream) {
+  if (nk < 0 || nk > 3 || stages < 1 || stages > 4 || stage < 0 || stage >= stages || table_len < stages)
+    return S2S_ERR_SHAPE;
+  const float* k[3] = {k1, k2, k3};
+  if (!t_out || !table || !counter) return S2S_ERR_NULL;
+  if (nk > 0 && (!x || !out)) return S2S_ERR_NULL;
+  if (out && !x) return S2S_ERR_NULL;
+  for (int j = 0; j < nk; ++j)
+    if (!k[j]) return S2S_ERR_NULL;
+  if (check_bn(B, n)) return S2S_ERR_SHAPE;
+  if (misaligned(x) || misaligned(out)) return S2S_ERR_ALIGN;
+  for (int j = 0; j < nk; ++j)
+    if (misaligned(k[j])) return S2S_ERR_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  const long n4 = n / 4;
+  const dim3 grid(dp_grid_x(n4), B), block(kThreads);
+  const f32x4 *X = (const f32x4*)x, *K0 = (const f32x4*)k1, *K1 = (const f32x4*)k2, *K2 = (const f32x4*)k3;
+  f32x4* O = (f32x4*)out;
+  if (!out) {
+    hipLaunchKernelGGL(rk_time_kernel, dim3(1), block, 0, s, t_out, B, table, counter, stages, stage, table_len);
+  } else {
+    switch (nk) {
+      case 0: hipLaunchKernelGGL(rk_stage_kernel<0>, grid, block, 0, s, X, X, X, X, 0.f, 0.f, 0.f, O, t_out, table,
+                                 counter, stages, stage, table_len, n4); break;
+      case 1: hipLaunchKernelGGL(rk_stage_kernel<1>, grid, block, 0, s, X, K0, K0, K0, c1, 0.f, 0.f, O, t_out, table,
+                                 counter, stages, stage, table_len, n4); break;
+      case 2: hipLaunchKernelGGL(rk_stage_kernel<2>, grid, block, 0, s, X, K0, K1, K0, c1, c2, 0.f, O, t_out, table,
+                                 counter, stages, stage, table_len, n4); break;
+      default: hipLaunchKernelGGL(rk_stage_kernel<3>, grid, block, 0, s, X, K0, K1, K2, c1, c2, c3, O, t_out, table,
+                                  counter, stages, stage, table_len, n4); break;
+    }
+  }
+  S2S_LAUNCH_CHECK();
+  return S2S_OK;
+}
+
+extern "C" int s2s_rk_combine(float* x, const float* k1, const float* k2, const float* k3, const float* k4, float c1,
+                              float c2, float c3, float c4, int nk, int* counter, int B, long n, void* stream) {
+  if (nk < 1 || nk > 4) return S2S_ERR_SHAPE;
+  const float* k[4] = {k1, k2, k3, k4};
+  if (!x || !counter) return S2S_ERR_NULL;
+  for (int j = 0; j < nk; ++j)
+    if (!k[j]) return S2S_ERR_NULL;
+  if (check_bn(B, n)) return S2S_ERR_SHAPE;
+  if (misaligned(x)) return S2S_ERR_ALIGN;
+  for (int j = 0; j < nk; ++j)
+    if (misaligned(k[j])) return S2S_ERR_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  const long n4 = n / 4;
+  const dim3 grid(dp_grid_x(n4), B), block(kThreads);
+  f32x4* X = (f32x4*)x;
+  const f32x4 *K0 = (const f32x4*)k1, *K1 = (const f32x4*)k2, *K2 = (const f32x4*)k3, *K3 = (const f32x4*)k4;
+  switch (nk) {
+    case 1: hipLaunchKernelGGL(rk_combine_kernel<1>, grid, block, 0, s, X, K0, K0, K0, K0, c1, 0.f, 0.f, 0.f, counter,
+                               n4); break;
+    case 2: hipLaunchKernelGGL(rk_combine_kernel<2>, grid, block, 0, s, X, K0, K1, K0, K0, c1, c2, 0.f, 0.f, counter,
+                               n4); break;
+    case 3: hipLaunchKernelGGL(rk_combine_kernel<3>, grid, block, 0, s, X, K0, K1, K2, K0, c1, c2, c3, 0.f, counter,
+                               n4); break;
+    default: hipLaunchKernelGGL(rk_combine_kernel<4>, grid, block, 0, s, X, K0, K1, K2, K3, c1, c2, c3, c4, counter,
+                                n4); break;
+  }
   S2S_LAUNCH_CHECK();
   return S2S_OK;
 }

@@ -15,7 +15,8 @@ names, argument meaning and return values, so the reference's training loop can 
 """
 from __future__ import annotations
 
-from typing import Any, Dict, Optional, Tuple
+from fractions import Fraction as _Fr
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
@@ -208,6 +209,195 @@ _DP_A = ((),
          (9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656),
          (35 / 384, 0.0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84))
 _DP_E = (-71 / 57600, 0.0, 71 / 16695, -71 / 1920, 17253 / 339200, -22 / 525, 1 / 40)
+
+
+# Explicit fixed-step Runge-Kutta tableaus with at most four stages: name -> (order, c, A rows, b), exact rationals.
+# ``rk4`` is the classical scheme, ``rk4_38`` Kutta's 3/8 rule; which of the two torchdyn's ``rk4`` name selects is
+# unpinned (the package is absent), so both are offered.
+_RK_TABLEAUS = {
+    "euler": (1, (_Fr(0),), ((),), (_Fr(1),)),
+    "midpoint": (2, (_Fr(0), _Fr(1, 2)), ((), (_Fr(1, 2),)), (_Fr(0), _Fr(1))),
+    "heun": (2, (_Fr(0), _Fr(1)), ((), (_Fr(1),)), (_Fr(1, 2), _Fr(1, 2))),
+    "rk4": (4, (_Fr(0), _Fr(1, 2), _Fr(1, 2), _Fr(1)),
+            ((), (_Fr(1, 2),), (_Fr(0), _Fr(1, 2)), (_Fr(0), _Fr(0), _Fr(1))),
+            (_Fr(1, 6), _Fr(1, 3), _Fr(1, 3), _Fr(1, 6))),
+    "rk4_38": (4, (_Fr(0), _Fr(1, 3), _Fr(2, 3), _Fr(1)),
+               ((), (_Fr(1, 3),), (_Fr(-1, 3), _Fr(1)), (_Fr(1), _Fr(-1), _Fr(1))),
+               (_Fr(1, 8), _Fr(3, 8), _Fr(3, 8), _Fr(1, 8))),
+}
+FIXED_STEP_METHODS = tuple(_RK_TABLEAUS)
+SOLVER_METHODS = ("dopri5",) + FIXED_STEP_METHODS
+
+
+def _check_fixed_step(method: str, num_steps) -> int:
+    if method not in _RK_TABLEAUS:
+        raise ValueError(f"fixed-step method must be one of {', '.join(map(repr, FIXED_STEP_METHODS))}, got {method!r}")
+    import operator
+    num_steps = operator.index(num_steps)
+    if num_steps < 1:
+        raise ValueError(f"num_steps must be >= 1, got {num_steps}")
+    return num_steps
+
+
+def fixed_step_evaluations(method: str, num_steps: int) -> int:
+    """Network evaluations of a ``num_steps``-step solve: ``num_steps`` times the number of stages."""
+    return _check_fixed_step(method, num_steps) * len(_RK_TABLEAUS[method][1])
+
+
+def fixed_step_coefficients(method: str, num_steps: int):
+    """(stage rows, weights) as the kernels get them: the non-zero entries ``(j, float(h * a_ij))`` of every row of A and
+    ``(j, float(h * b_j))`` of b, ascending j, h = 1 / num_steps; each product is formed in double (the launch rounds it
+    to fp32 once, as ``ops.axpy_`` rounds its scalar)."""
+    num_steps = _check_fixed_step(method, num_steps)
+    _, _, A, b = _RK_TABLEAUS[method]
+    h = 1.0 / num_steps
+    rows = [[(j, float(h * float(a))) for j, a in enumerate(row) if a != 0] for row in A]
+    return rows, [(j, float(h * float(w))) for j, w in enumerate(b) if w != 0]
+
+
+def fixed_step_node_times(method: str, num_steps: int) -> torch.Tensor:
+    """The fp32 table [num_steps * stages] of node times on the host: entry (k, i) is ``k * h + c_i * h`` formed in
+    double and rounded once, as the Euler path forms ``k * dt``."""
+    num_steps = _check_fixed_step(method, num_steps)
+    c = _RK_TABLEAUS[method][1]
+    h = 1.0 / num_steps
+    return torch.tensor([k * h + float(ci) * h for k in range(num_steps) for ci in c], dtype=torch.float32)
+
+
+class _FixedStepRK:
+    """A fixed-step explicit Runge-Kutta solve of ``dx/dt = f(t, x)`` on the grid of the Euler path (``num_steps`` steps
+    of h = 1 / num_steps from 0 to 1) with the fused kernels of csrc/ode.hip: per step one
+    stage launch and one evaluation per stage, then one combine launch.  The node times sit in a device table that the
+    stage launches index with a device-side step counter, which only the combine launch advances, so ``step`` takes no
+    host-side argument, allocates nothing outside ``f`` and never synchronises: ``_FixedStepGraph`` captures it whole.
+    ``f`` must return a tensor of its own on every call (the k_j of one step are read together)."""
+
+    def __init__(self, f, x: torch.Tensor, num_steps: int, method: str):
+        num_steps = _check_fixed_step(method, num_steps)
+        if not x.is_cuda:
+            raise RuntimeError("stain2stain_amd: the fixed-step samplers need GPU tensors (there is no CPU path)")
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() < 2 or x.numel() == 0 or (x[0].numel() % 4):
+            raise RuntimeError("stain2stain_amd: the fixed-step samplers want contiguous fp32 [B, ...] samples of a "
+                               "multiple of 4 elements")
+        self.f, self.x, self.num_steps, self.method = f, x, num_steps, method
+        self.stages = len(_RK_TABLEAUS[method][1])
+        self.rows, self.weights = fixed_step_coefficients(method, num_steps)
+        self.xs = torch.empty_like(x) if self.stages > 1 else None
+        self.t = torch.zeros((x.shape[0],), dtype=torch.float32, device=x.device)
+        self.table = fixed_step_node_times(method, num_steps).to(x.device)
+        self.counter = torch.zeros((1,), dtype=torch.int32, device=x.device)
+
+    def step(self) -> List[torch.Tensor]:
+        """One step: x advanced in place, the counter moved on; returns the k_j."""
+        ks: List[torch.Tensor] = []
+        for i, row in enumerate(self.rows):
+            terms = [(c, ks[j]) for j, c in row]
+            out = self.xs if terms else None              # a row of zeros evaluates on x itself: the node time alone
+            ops.rk_stage_(self.x, terms, out, self.t, self.table, self.counter, self.stages, i)
+            ks.append(self.f(self.t, self.x if out is None else out).contiguous())
+        ops.rk_combine_(self.x, [(c, ks[j]) for j, c in self.weights], self.counter)
+        return ks
+
+    def solve(self) -> torch.Tensor:
+        self.counter.zero_()
+        for _ in range(self.num_steps):
+            self.step()
+        return self.x
+
+
+@torch.no_grad()
+def fixed_step_integrate(f, x: torch.Tensor, num_steps: int, method: str = "rk4") -> torch.Tensor:
+    """``num_steps`` steps of the explicit Runge-Kutta scheme ``method`` (one of ``FIXED_STEP_METHODS``) from t = 0 to
+    t = 1 for a callable ``f(t[B], x)``; ``x`` (contiguous fp32 on the GPU) is advanced in place and returned, like
+    ``euler_integrate``, to which ``method="euler"`` delegates.  ``num_steps`` evaluations per stage of the scheme: 2 per
+    step for ``midpoint`` and ``heun``, 4 for ``rk4`` (classical) and ``rk4_38`` (3/8 rule).  Every sample is stepped
+    on the same grid, so a sample's result does not depend on its batch mates.  The stage and combine arithmetic is the
+    chain ``clone`` + ``ops.axpy_`` per non-zero coefficient, bit for bit, in one launch each."""
+    num_steps = _check_fixed_step(method, num_steps)
+    if method == "euler":
+        return euler_integrate(f, x, num_steps)
+    return _FixedStepRK(f, x, num_steps, method).solve()
+
+
+class _FixedStepGraph:
+    """One whole step of ``_FixedStepRK`` captured as a hipGraph on one stream (no forked branches): the s evaluations,
+    the stage launches and the combine; the k_j are the network outputs the capture allocated, read in place.  A solve
+    is ``num_steps`` replays.  Cached on the network as ``net._s2s_rk_graph`` until the batch shape, ``num_steps``, the
+    method, the parameters or ``engine.mutation_epoch`` change; ``close()`` releases it."""
+
+    def __init__(self, net, x_like: torch.Tensor, num_steps: int, method: str):
+        self.net = net
+        self.key = self._key(net, x_like, num_steps, method)
+        self.solver = s = _FixedStepRK(net, x_like.detach().float().contiguous().clone(), num_steps, method)
+        side = torch.cuda.Stream(device=x_like.device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                   # warm-up: packed weights, folded BN constants, LDS attributes
+            for _ in range(2):
+                net(s.t, s.x)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with ops.capture_graph(self.graph):
+            self.ks = s.step()
+
+    @staticmethod
+    def _key(net, x, num_steps, method):
+        from . import engine
+        return (tuple(x.shape), int(num_steps), str(method), engine.mutation_epoch[0],
+                tuple(p._version for p in _params(net)))
+
+    def matches(self, net, x, num_steps, method) -> bool:
+        return self.graph is not None and net is self.net and self.key == self._key(net, x, num_steps, method)
+
+    def solve(self, source: torch.Tensor) -> torch.Tensor:
+        if self.graph is None:
+            raise RuntimeError("stain2stain_amd: this fixed-step graph has been closed")
+        s = self.solver
+        s.x.copy_(source)
+        s.counter.zero_()
+        for _ in range(s.num_steps):
+            self.graph.replay()
+        return s.x.clone()
+
+    def close(self) -> None:
+        """Release the graph and its private pool now (it sits in a cycle with its network)."""
+        self.graph = None
+        self.ks = None
+        if getattr(self.net, "_s2s_rk_graph", None) is self:
+            try:
+                object.__delattr__(self.net, "_s2s_rk_graph")
+            except Exception:  # noqa: BLE001
+                pass
+
+
+def _cached_fixed_step_graph(net, x: torch.Tensor, num_steps: int, method: str) -> _FixedStepGraph:
+    g = getattr(net, "_s2s_rk_graph", None)
+    if g is None or not g.matches(net, x, num_steps, method):
+        if g is not None:
+            g.close()                      # the superseded graph goes now, not whenever the cyclic collector finds it
+        g = _FixedStepGraph(net, x, num_steps, method)
+        try:
+            object.__setattr__(net, "_s2s_rk_graph", g)        # a plain attribute, not a registered sub-module
+        except Exception:  # noqa: BLE001 -- a callable that takes no attributes: rebuild next time
+            pass
+    return g
+
+
+@torch.no_grad()
+def fixed_step_generate(net, source_img: torch.Tensor, num_steps: int, method: str = "rk4",
+                        graph: bool = False) -> torch.Tensor:
+    """x(0) = source, ``num_steps`` steps of the Runge-Kutta scheme ``method`` (``FIXED_STEP_METHODS``) to t = 1, network
+    in eval mode (its mode is restored); returns x(1).  ``graph=True`` replays one captured whole step ``num_steps``
+    times (``_FixedStepGraph``, cached on the network until its parameters, the batch shape, ``num_steps`` or the method
+    change): same kernels, same results.  ``method="euler"`` is ``euler_generate``."""
+    num_steps = _check_fixed_step(method, num_steps)
+    if method == "euler":
+        return euler_generate(net, source_img, num_steps, graph=graph)
+    with _eval_mode(net):
+        x = _prep_source(source_img)
+        if not graph:
+            return fixed_step_integrate(net, x, num_steps, method)
+        return _cached_fixed_step_graph(net, x, num_steps, method).solve(x)
 
 
 @torch.no_grad()
@@ -470,17 +660,27 @@ def _solver_setting(solver, name: str, default):
     return default
 
 
+def _solver_method(solver, method: Optional[str] = None) -> str:
+    """The solver name a ``generate`` call runs: ``method`` when given, else ``solver.solver`` (attribute or keyword of a
+    partial), else dopri5; a name outside ``SOLVER_METHODS`` raises ValueError before anything touches the GPU."""
+    method = method or _solver_setting(solver, "solver", "dopri5")
+    if not isinstance(method, str) or method not in SOLVER_METHODS:
+        raise ValueError(f"solver method must be one of {', '.join(map(repr, SOLVER_METHODS))}, got {method!r}")
+    return method
+
+
 def _solve(module, f, source_img: torch.Tensor, num_steps: int, method: Optional[str], atol: Optional[float],
            rtol: Optional[float], graph: bool = False, per_sample: bool = False) -> torch.Tensor:
     """The ODE solve shared by every ``generate``: like the reference it refuses to run without a solver, puts the
     module in eval mode and LEAVES it there (``self.eval()``, conditional_flow_matching.py:147-150), integrates with
     the solver's method / tolerances (dopri5, 1e-4 when it names none) and returns the end point x(1).  ``method``
-    overrides the solver's choice: "euler" is the ``num_steps`` fixed-step solve of BASELINE.json configs[3].
+    overrides the solver's choice: "euler" is the ``num_steps`` fixed-step solve of BASELINE.json configs[3], the other
+    names of ``FIXED_STEP_METHODS`` ("midpoint", "heun", "rk4", "rk4_38") ``num_steps`` steps of that Runge-Kutta scheme.
     ``per_sample=True`` (dopri5 only): every sample gets its own step size, so it does not depend on its batch mates."""
     if module.solver is None:
         raise ValueError("Solver is not initialized. Cannot perform inference.")
     module.eval()
-    method = method or _solver_setting(module.solver, "solver", "dopri5")
+    method = _solver_method(module.solver, method)
     atol = _solver_setting(module.solver, "atol", 1e-4) if atol is None else atol
     rtol = _solver_setting(module.solver, "rtol", 1e-4) if rtol is None else rtol
     x = _prep_source(source_img)
@@ -503,7 +703,15 @@ def _solve(module, f, source_img: torch.Tensor, num_steps: int, method: Optional
         if graph:
             return GraphedVelocity(f, x, 1.0 / num_steps).solve_euler(x, num_steps)
         return euler_integrate(f, x, num_steps)
-    raise ValueError(f"solver method must be 'dopri5' or 'euler', got {method!r}")
+    if isinstance(method, str) and method in _RK_TABLEAUS:
+        if not graph:
+            return fixed_step_integrate(f, x, num_steps, method)
+        g = _FixedStepGraph(f, x, num_steps, method)
+        try:
+            return g.solve(x)
+        finally:
+            g.close()
+    raise ValueError(f"solver method must be one of {', '.join(map(repr, SOLVER_METHODS))}, got {method!r}")
 
 
 class ConditionalFlowMatchingModule(_Base):

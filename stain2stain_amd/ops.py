@@ -915,6 +915,56 @@ def dp_commit_(y, y_new, k1, k7, state) -> None:
                                      _stream()), "dp_commit")
 
 
+def _f32_rows(t: torch.Tensor, B: int, n: int, what: str) -> int:
+    """Pointer of a contiguous fp32 GPU tensor of B samples of n elements each, n % 4 == 0, 16-byte aligned."""
+    p = _f32(t)
+    if t.dim() < 1 or t.shape[0] != B or t.numel() != B * n:
+        raise RuntimeError(f"stain2stain_amd: {what} must hold {B} samples of {n} elements, got {list(t.shape)}")
+    if p % 16:
+        raise RuntimeError(f"stain2stain_amd: {what} must be 16-byte aligned")
+    return p
+
+
+def _rk_shape(x: torch.Tensor) -> Tuple[int, int]:
+    if x.dim() < 2 or x.numel() == 0 or (x.numel() // x.shape[0]) % 4:
+        raise RuntimeError("stain2stain_amd: the Runge-Kutta kernels want [B, ...] samples of a multiple of 4 elements")
+    return x.shape[0], x.numel() // x.shape[0]
+
+
+# fixed-step Runge-Kutta (ode.hip): x, k_j, out fp32 [B, ...]; t_out float32 [B]; table float32 [num_steps * stages];
+# counter int32 [1].  ``terms``: the (coefficient, k) pairs of the non-zero entries of a tableau row, ascending j.
+def rk_stage_(x, terms, out, t_out, table, counter, stages: int, stage: int) -> None:
+    """out = x + sum c_j k_j (``out`` None and no terms: only the node time); t_out[:] = table[counter * stages + stage]."""
+    B, n = _rk_shape(x)
+    if len(terms) > 3 or (out is None and terms):
+        raise RuntimeError("stain2stain_amd: rk_stage takes at most three terms, and an output when it has any")
+    if not (0 <= int(stage) < int(stages) <= 4) or table.numel() < stages or table.dim() != 1:
+        raise RuntimeError("stain2stain_amd: rk_stage wants 0 <= stage < stages <= 4 and a table of whole steps")
+    if t_out.shape != (B,) or counter.numel() != 1:
+        raise RuntimeError(f"stain2stain_amd: rk_stage wants t_out of shape [{B}] and a counter of one element")
+    if out is not None and (out.data_ptr() == x.data_ptr() or any(k.data_ptr() == out.data_ptr() for _, k in terms)):
+        raise RuntimeError("stain2stain_amd: rk_stage is out of place: out must not be x or a k")
+    xp = _f32_rows(x, B, n, "x")
+    op = 0 if out is None else _f32_rows(out, B, n, "out")
+    kp = [_f32_rows(k, B, n, "k") for _, k in terms] + [0] * (3 - len(terms))
+    cs = [float(c) for c, _ in terms] + [0.0] * (3 - len(terms))
+    _native.check(_L().s2s_rk_stage(xp, *kp, *cs, len(terms), op, _f32(t_out), _f32(table), _i32(counter), int(stages),
+                                    int(stage), table.numel(), B, n, _stream()), "rk_stage")
+
+
+def rk_combine_(x, terms, counter) -> None:
+    """x += sum c_j k_j in place (one to four terms); counter += 1 on the device."""
+    B, n = _rk_shape(x)
+    if not 1 <= len(terms) <= 4:
+        raise RuntimeError("stain2stain_amd: rk_combine takes one to four terms")
+    if counter.numel() != 1 or any(k.data_ptr() == x.data_ptr() for _, k in terms):
+        raise RuntimeError("stain2stain_amd: rk_combine wants a counter of one element and k tensors other than x")
+    xp = _f32_rows(x, B, n, "x")
+    kp = [_f32_rows(k, B, n, "k") for _, k in terms] + [0] * (4 - len(terms))
+    cs = [float(c) for c, _ in terms] + [0.0] * (4 - len(terms))
+    _native.check(_L().s2s_rk_combine(xp, *kp, *cs, len(terms), _i32(counter), B, n, _stream()), "rk_combine")
+
+
 def euler_tick_(t: torch.Tensor, table: torch.Tensor, counter: torch.Tensor) -> None:
     """t[:] = table[counter]; counter += 1 (device side; see s2s_euler_tick)."""
     if counter.dtype != torch.int32 or table.dtype != torch.float32:

@@ -74,7 +74,8 @@ def translate_region(image: torch.Tensor, sampler: Callable, *, tile: int = 256,
     a copy), pixels contiguous within a row.  ``sampler``: called with fp32 [batch, 3, tile, tile] on the GPU (the
     normalised tiles, ``(u / 255 - 0.5) / 0.5``); returns fp32 [batch, 3, tile, tile] or a tuple (image, probabilities
     [batch, Cm, tile, tile]) with Cm <= 5.  For a ``FlowUNet``: ``lambda x: euler_generate(net, x, 50, graph=True)``;
-    for ``MultiTaskFlowMatchingModule``: ``multitask_sampler(module, 50)``.  The reference's adaptive solver, one step size
+    for ``MultiTaskFlowMatchingModule``: ``multitask_sampler(module, 50)``.  A higher-order fixed-step scheme with fewer
+    evaluations: ``lambda x: fixed_step_generate(net, x, 6, "rk4", graph=True)``.  The reference's adaptive solver, one step size
     per tile: ``lambda x: dopri5_generate(net, x, per_sample=True, graph=True)`` or
     ``multitask_sampler(module, 1, method="dopri5")``.
 
@@ -214,12 +215,16 @@ def multitask_sampler(module, num_steps: int, graph: bool = True, *, method: str
     module's parameters change).  The module is put in eval mode, as its ``generate`` does.
     ``method="dopri5"``: the reference's adaptive solver at ``atol`` / ``rtol`` instead, with a step size per tile
     (``dopri5_integrate(..., per_sample=True)``), so every tile is independent of its batch mates; ``graph`` then
-    captures one whole attempted step; ``num_steps`` plays no role."""
+    captures one whole attempted step; ``num_steps`` plays no role.  ``method`` "midpoint", "heun", "rk4" or "rk4_38":
+    ``num_steps`` steps of that fixed-step Runge-Kutta scheme (``fixed_step_integrate``); ``graph`` then captures one
+    whole step (its evaluations, stage launches and combine)."""
     from . import engine
-    from .flow_matching import GraphedVelocity, _Dopri5Graph, _prep_source, dopri5_integrate, euler_integrate
+    from .flow_matching import (SOLVER_METHODS, GraphedVelocity, _Dopri5Graph, _FixedStepGraph, _prep_source,
+                                dopri5_integrate, euler_integrate, fixed_step_integrate)
     num_steps = operator.index(num_steps)
-    if method not in ("euler", "dopri5"):
-        raise ValueError(f"method must be 'euler' or 'dopri5', got {method!r}")
+    if method not in SOLVER_METHODS:
+        raise ValueError(f"method must be one of {', '.join(map(repr, SOLVER_METHODS))}, got {method!r}")
+    rk = method not in ("euler", "dopri5")
     if num_steps < 1:
         raise ValueError(f"num_steps must be >= 1, got {num_steps}")
     flow = module.forward_flow                            # one bound method: the graph's key
@@ -231,6 +236,8 @@ def multitask_sampler(module, num_steps: int, graph: bool = True, *, method: str
         probs = torch.softmax(logits, dim=1) if module.num_classes is not None else torch.sigmoid(logits)
         if method == "dopri5" and not graph:
             return dopri5_integrate(flow, _prep_source(x), atol, rtol, per_sample=True), probs.float()
+        if rk and not graph:
+            return fixed_step_integrate(flow, _prep_source(x), num_steps, method), probs.float()
         if not graph:
             return euler_integrate(flow, _prep_source(x), num_steps), probs.float()
         key = (tuple(x.shape), engine.mutation_epoch[0], tuple(p._version for p in module.parameters()))
@@ -238,8 +245,9 @@ def multitask_sampler(module, num_steps: int, graph: bool = True, *, method: str
             if state["gv"] is not None:
                 state["gv"].close()
             state["gv"], state["key"] = (_Dopri5Graph(flow, _prep_source(x), atol, rtol, 1000) if method == "dopri5"
+                                         else _FixedStepGraph(flow, _prep_source(x), num_steps, method) if rk
                                          else GraphedVelocity(flow, _prep_source(x), 1.0 / num_steps)), key
-        if method == "dopri5":
+        if method == "dopri5" or rk:
             return state["gv"].solve(_prep_source(x)), probs.float()
         return state["gv"].solve_euler(_prep_source(x), num_steps), probs.float()
 
