@@ -2,7 +2,7 @@
 """Headline benchmark: paired 256x256 stain tiles/s for one full optimisation step of the
 flow-matching U-Net (sample -> forward -> loss -> backward -> gradient all-reduce -> Adam).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,7 +12,10 @@ features [64,128,256,512,1024], 3x256x256 tiles, batch 16 per GPU, bf16 MFMA com
 accumulation / BatchNorm statistics / master weights, synthetic tiles U(-1,1), random-init weights.
 Weak scaling: every rank steps its own 16 tiles; the only collective is the gradient all-reduce.
 
-One JSON line on rank 0; see README / DESIGN.md for the roofline and cpu_baseline objects.
+One JSON line on rank 0.  A plain run sets up, warms up, times the K steps (the conv roofline comes from HIP-event
+brackets inside them) and prints the line.  ``--full`` adds every leg that takes a run of its own: the other launch mode
+of the same trainer, the CPU baselines, "sample", "fp32_parity", "dropin", "multitask" and the pix2pix G + D step; see
+README / DESIGN.md for the roofline and cpu_baseline objects.
 """
 import argparse
 import gc
@@ -191,7 +194,7 @@ def _other_leg(trainer, step_fn, steps: int, use_dist: bool):
 
 
 def sample_leg(dev) -> dict:
-    """BASELINE.json configs[3] inside the default line: the eval-mode network (BatchNorm folded into the conv epilogue),
+    """BASELINE.json configs[3] inside the --full line: the eval-mode network (BatchNorm folded into the conv epilogue),
     50 fixed Euler steps, batch 32 -- and batch 1, the reference's own use (src/infer_simple_flowmatching.py:73-83) --
     launched eagerly and as one replayed hipGraph per Euler step.  Synchronised wall time of whole solves."""
     from stain2stain_amd import FlowUNet, euler_generate
@@ -510,7 +513,7 @@ def pix2pix_bench(args, dev, rank: int, world: int, use_dist: bool, dump: str = 
     # (the second launch mode is timed at world size 1 only: a captured multi-rank RCCL exchange has never run on hardware
     #  available to the builder, and nothing untested goes between the timed region and the JSON line of a scaling run)
     other_ms = (_other_leg(tr, lambda i: tr.step(*data[i % 4]), steps, use_dist)
-                if (graph_ok and world == 1 and not args.no_extras) else None)
+                if (args.full and graph_ok and world == 1 and not args.no_extras) else None)
     agg, by_net = {}, {}
     for name, work, e0, e1 in prof:
         base, _, net = name.partition("@")          # brackets are tagged with the network whose pass issued them
@@ -576,8 +579,14 @@ def main() -> None:
     ap.add_argument("--batch", type=int, default=BATCH_PER_GPU, help="tiles per GPU (default: the headline 16)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--tile", type=int, default=TILE, help="tile edge (default 256; 512 = BASELINE.json configs[4])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pix2pix", action="store_true", help="skip the second timed loop (the pix2pix G + D step)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed loop, also run every leg that takes a run of its own: the other launch mode of "
+                         "the same trainer (graph_ms_per_step / eager_ms_per_step), the CPU baselines, \"sample\", "
+                         "\"fp32_parity\", \"dropin\", \"multitask\" and the pix2pix G + D step (\"pix2pix\").  Off by "
+                         "default: a plain run does only what its headline figure needs.  --no-cpu-baseline, --no-pix2pix "
+                         "and --no-extras narrow a --full run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-pix2pix", action="store_true", help="--full: skip the second timed loop (the pix2pix G + D step)")
     ap.add_argument("--sync-batchnorm", action="store_true",
                     help="BatchNorm statistics over the global batch (configs/trainer/ddp.yaml:9; off in the stain experiments)")
     ap.add_argument("--sharded-optimizer", action="store_true",
@@ -598,9 +607,10 @@ def main() -> None:
     ap.add_argument("--train-graph", action="store_true",
                     help="training modes: time the replay of one captured hipGraph per optimisation step in the headline "
                          "loop (default: eager launches, which overlap the side-stream weight gradients better on this "
-                         "ROCm; the line reports the other mode's ms/step beside the headline either way)")
+                         "ROCm; with --full the line reports the other mode's ms/step beside the headline either way)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary legs of the default line (\"sample\": configs[3], \"fp32_parity\")")
+                    help="--full: skip the other launch mode's leg and the secondary legs of the line "
+                         "(\"sample\": configs[3], \"fp32_parity\", \"dropin\", \"multitask\")")
     ap.add_argument("--h2d", action="store_true",
                     help="PCIe-inclusive variant for DESIGN.md: every step copies a fresh uint8 batch from pinned host "
                          "memory and runs the GPU crop/flip/normalise kernel before the optimisation step")
@@ -800,7 +810,7 @@ def main() -> None:
     if args.dump_outputs and rank == 0:          # before the other launch mode's leg steps the same trainer further
         _dump_outputs(args.dump_outputs, _step_outputs(loss, [net]))
     other_ms = None
-    if graph_ok and world == 1 and not args.no_extras:      # (world size 1 only: see pix2pix_bench)
+    if args.full and graph_ok and world == 1 and not args.no_extras:      # (world size 1 only: see pix2pix_bench)
         other_ms = _other_leg(trainer, lambda i: trainer.step(*pool[i % 4], ts[i % len(ts)]), args.steps, use_dist)
     gc_pause.resume()
     if ms0 is not None:
@@ -862,7 +872,7 @@ def main() -> None:
                                  "side stream (S2S_WGRAD_STREAM=0 disables it, e.g. for rocprofv3 kernel statistics)" % every},
             "kernels": kernels,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
     rc = rccl_object(dev, world, use_dist)            # (a collective: every rank calls)
     if rank == 0:
@@ -872,7 +882,7 @@ def main() -> None:
     p2p = None
     default_line = args.precision == "bf16" and not args.h2d and not args.breakdown
     extras = {}
-    if default_line and world == 1 and not args.no_extras and TILE == 256:
+    if args.full and default_line and world == 1 and not args.no_extras and TILE == 256:
         del trainer, net
         trainer = net = None
         torch.cuda.empty_cache()
@@ -885,7 +895,7 @@ def main() -> None:
         mt = multitask_bench(args, dev, rank, world, use_dist, 512, 8, max(4, args.steps // 2), 2)
         extras["multitask"] = {k: mt[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "dtype", "config", "roofline", "kernels")}
         torch.cuda.empty_cache()
-    if not args.no_pix2pix and default_line:
+    if args.full and not args.no_pix2pix and default_line:
         del trainer, net
         torch.cuda.empty_cache()
         p2p = pix2pix_bench(args, dev, rank, world, use_dist)

@@ -9,7 +9,7 @@ TAG=${1:-r02_x}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-python bench.py --steps 30 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 30 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done"
 export S2S_WGRAD_STREAM=0
 CFM="--no-pix2pix --no-cpu-baseline --no-extras"

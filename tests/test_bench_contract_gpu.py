@@ -21,8 +21,27 @@ def _run(*extra, env=None, steps=2):
     return json.loads(lines[0])
 
 
-def test_training_line_has_the_contract_keys():
+def test_plain_run_times_the_headline_step_and_nothing_else():
+    """A run without --full sets up, warms up, times its steps and prints the line: the headline keys and the roofline of
+    the event-bracketed steps are there, no leg that takes a run of its own is."""
     d = _run()
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline", "kernels"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True
+    assert d["dtype"] == "bf16" and d["unit"] == "tiles/s" and "full CFM optimisation step" in d["metric"]
+    assert abs(d["value"] - 16 * 1000.0 / d["ms_per_step"]) < 0.01 * d["value"]
+    assert d["roofline"]["bound"] == "mfma" and d["roofline"]["achieved"] > 100
+    for k in ("cpu_baseline", "pix2pix", "sample", "fp32_parity", "dropin", "multitask"):
+        assert k not in d, k
+    assert d["config"]["launch"].startswith("eager") and d["config"]["graph_ms_per_step"] is None
+    # the flags that narrow a --full run change nothing without it
+    n = _run("--no-pix2pix", "--no-cpu-baseline", "--no-extras")
+    assert set(n) == set(d) and n["config"]["loss_bits"] == d["config"]["loss_bits"]
+
+
+def test_training_line_has_the_contract_keys():
+    d = _run("--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -41,7 +60,7 @@ def test_training_line_has_the_contract_keys():
     # eager launches in the headline loop, the hipGraph replay of the same trainer timed beside it
     assert d["config"]["launch"].startswith("eager") and d["config"]["graph_ms_per_step"] > 0
     assert p["config"]["launch"].startswith("eager") and p["config"]["graph_ms_per_step"] > 0
-    # the driver's default line times what DESIGN quotes -- configs[3] (batch 32 x 50 Euler steps, eager
+    # the --full line times what DESIGN quotes -- configs[3] (batch 32 x 50 Euler steps, eager
     # and graphed, and the reference's batch 1) and the fp32 parity mode of the headline step
     sm = d["sample"]
     for b in ("batch32", "batch1"):
@@ -56,8 +75,8 @@ def test_training_line_has_the_contract_keys():
 def test_dropin_path_is_within_ten_percent_of_the_fused_trainer():
     """what a user of the reference gets after the ``_target_`` swap -- FlowUNet under autograd inside
     ConditionalFlowMatchingModule, zero_grad / training_step / backward / optimizer.step with stain2stain_amd.FusedAdam --
-    timed in the default line under the headline's contract, at most 1.10 x the fused trainer's step."""
-    d = _run("--no-pix2pix", "--no-cpu-baseline", steps=16)
+    timed in the --full line under the headline's contract, at most 1.10 x the fused trainer's step."""
+    d = _run("--full", "--no-pix2pix", "--no-cpu-baseline", steps=16)
     dr = d["dropin"]
     assert dr["unit"] == "tiles/s" and dr["dtype"] == "bf16" and "training_step" in dr["metric"]
     assert dr["fused_adam"]["ms_per_step"] > 0 and dr["torch_adam"]["ms_per_step"] > 0
@@ -115,9 +134,10 @@ def test_rccl_path_in_a_fresh_process_matches_the_single_process_run():
     stream, joined before Adam, 1/world folded into the update) and its final losses -- CFM step and pix2pix G + D step --
     must equal the run without any collective BIT FOR BIT; the reduce-scatter / sharded-Adam / all-gather mode as well."""
     port = {"MASTER_ADDR": "127.0.0.1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"}
-    plain = _run("--no-cpu-baseline", steps=3)
-    ddp = _run("--no-cpu-baseline", steps=3, env={"S2S_FORCE_DDP": "1", "MASTER_PORT": "29611", **port})
-    rs = _run("--no-cpu-baseline", "--sharded-optimizer", steps=3, env={"S2S_FORCE_DDP": "1", "MASTER_PORT": "29612", **port})
+    plain = _run("--full", "--no-cpu-baseline", steps=3)
+    ddp = _run("--full", "--no-cpu-baseline", steps=3, env={"S2S_FORCE_DDP": "1", "MASTER_PORT": "29611", **port})
+    rs = _run("--full", "--no-cpu-baseline", "--sharded-optimizer", steps=3,
+              env={"S2S_FORCE_DDP": "1", "MASTER_PORT": "29612", **port})
     assert plain["config"]["grad_exchange"] == "none" and ddp["config"]["grad_exchange"] == "allreduce"
     assert rs["config"]["grad_exchange"] == "reduce_scatter"
     assert max(ddp["config"]["buckets_mb"]) <= 16.0 and len(ddp["config"]["buckets_mb"]) == 14
