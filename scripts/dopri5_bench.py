@@ -29,7 +29,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1984)
     a = ap.parse_args()
     from stain2stain_amd import FlowUNet, dopri5_generate, dopri5_integrate
-    from stain2stain_amd.flow_matching import GraphedVelocity, _eval_mode, _prep_source
+    from stain2stain_amd.samplers import GraphedVelocity, _eval_mode, _prep_source
     torch.manual_seed(a.seed)
     net = FlowUNet(precision="bf16").cuda().eval()
 

@@ -34,7 +34,7 @@ def step_bytes_in_T(method):
     """(fused, chain) bytes per step in units of T, from the tableau: a fused stage with m non-zero coefficients reads x
     and m k's and writes out (2 + m; a row of zeros launches nothing that scales with T), the fused combine reads and
     writes x and reads its m k's (2 + m); the chain clones x (2) and runs one axpy (3) per non-zero coefficient."""
-    from stain2stain_amd.flow_matching import fixed_step_coefficients
+    from stain2stain_amd.samplers import fixed_step_coefficients
     rows, weights = fixed_step_coefficients(method, 1)
     fused = sum(2 + len(r) for r in rows if r) + 2 + len(weights)
     chain = sum(2 + 3 * len(r) for r in rows if r) + 3 * len(weights)
@@ -77,7 +77,7 @@ def fused_step(x, ks, rows, weights, xs, t, table, counter):
 
 
 def kernels_mode(a, methods):
-    from stain2stain_amd.flow_matching import fixed_step_coefficients, fixed_step_node_times
+    from stain2stain_amd.samplers import fixed_step_coefficients, fixed_step_node_times
     inner = a.inner
     for B in [int(v) for v in a.batches.split(",")]:
         g = torch.Generator().manual_seed(a.seed + B)
@@ -130,7 +130,7 @@ def kernels_mode(a, methods):
 
 def trace_mode(a, net, methods):
     from stain2stain_amd import fixed_step_generate
-    from stain2stain_amd.flow_matching import fixed_step_coefficients
+    from stain2stain_amd.samplers import fixed_step_coefficients
     B = int(a.batches.split(",")[-1])
     g = torch.Generator().manual_seed(a.seed)
     x = (torch.rand(B, 3, a.size, a.size, generator=g) * 2 - 1).cuda()
@@ -162,7 +162,7 @@ def main():
     ap.add_argument("--trace-steps", type=int, default=2)
     a = ap.parse_args()
     from stain2stain_amd import FIXED_STEP_METHODS, FlowUNet, checkpoint, dopri5_generate, fixed_step_generate
-    from stain2stain_amd.flow_matching import fixed_step_evaluations
+    from stain2stain_amd.samplers import fixed_step_evaluations
     rk = [m for m in FIXED_STEP_METHODS if m != "euler"]
     for m in FIXED_STEP_METHODS:
         fb, cb = step_bytes_in_T(m)

@@ -26,7 +26,7 @@ namespace {
 enum { S_T, S_H, S_ACC, S_REJ, S_REJECTED, S_DONE, S_ACCEPT, S_AUX, DP_SLOTS };   // S_AUX: d1 in init, then last norm
 enum { ST_ACTIVE, ST_LIMIT, ST_ATTEMPTS, ST_WORDS = 4 };
 
-// Dormand-Prince nodes, stage rows (row 6 = the 5th-order weights) and error weights, as flow_matching._DP_*.
+// Dormand-Prince nodes, stage rows (row 6 = the 5th-order weights) and error weights, as samplers._DP_*.
 // Row 0 is the initial-step probe y + h0 k1 of s2s_dp_init.
 __device__ constexpr double kC[7] = {1.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};
 __device__ constexpr double kA[7][6] = {

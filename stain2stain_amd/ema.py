@@ -83,7 +83,7 @@ def _touch(tensors: Sequence[torch.Tensor]) -> None:
     """The EMA kernels write through raw pointers, behind torch's version counters.  The averaged network's packed MFMA
     operands are cached by (pointer, version) of their master weight (engine.ConvBN.packed; the forward refreshes stale
     ones in one batched launch, engine.repack_stale) and a sampler's captured graph by the parameter versions
-    (flow_matching.GraphedVelocity): bumping the versions here is what makes both see the new average.  The folded
+    (samplers.GraphedVelocity): bumping the versions here is what makes both see the new average.  The folded
     BatchNorm constants are keyed on engine.mutation_epoch, which the caller bumps."""
     with torch.no_grad():
         torch.autograd.graph.increment_version(list(tensors))

@@ -1000,8 +1000,8 @@ def adam_hyper(step: int, lr: float, beta1: float, beta2: float, eps: float, wei
 
 class capture_graph:
     """``torch.cuda.graph(g)`` with Python's cyclic collector out of the way.  A collection that runs DURING a capture can
-    destroy an earlier, unreachable ``torch.cuda.CUDAGraph`` (e.g. the sampler's GraphedVelocity, which forms a cycle with
-    its network): hipGraphExecDestroy / the release of its private memory pool inside another stream capture aborts the
+    destroy an earlier, unreachable ``torch.cuda.CUDAGraph`` (e.g. a sampler's capture, ``samplers._GraphedStep``, which
+    forms a cycle with its network): hipGraphExecDestroy / the release of its private memory pool inside another stream capture aborts the
     process (seen on ROCm 7 / torch 2.10, whose ``torch.cuda.graph`` no longer collects on entry).  So: collect first,
     keep the collector off while capturing, restore it afterwards.
 

@@ -12,6 +12,7 @@ image at a time at batch 1; ``translate_region`` is the loop around them (INTEGR
 from __future__ import annotations
 
 import operator
+import types
 from typing import Callable, Dict, List, Optional
 
 import torch
@@ -218,37 +219,20 @@ def multitask_sampler(module, num_steps: int, graph: bool = True, *, method: str
     captures one whole attempted step; ``num_steps`` plays no role.  ``method`` "midpoint", "heun", "rk4" or "rk4_38":
     ``num_steps`` steps of that fixed-step Runge-Kutta scheme (``fixed_step_integrate``); ``graph`` then captures one
     whole step (its evaluations, stage launches and combine)."""
-    from . import engine
-    from .flow_matching import (SOLVER_METHODS, GraphedVelocity, _Dopri5Graph, _FixedStepGraph, _prep_source,
-                                dopri5_integrate, euler_integrate, fixed_step_integrate)
+    from .samplers import SOLVER_METHODS, _prep_source, solve
     num_steps = operator.index(num_steps)
     if method not in SOLVER_METHODS:
         raise ValueError(f"method must be one of {', '.join(map(repr, SOLVER_METHODS))}, got {method!r}")
-    rk = method not in ("euler", "dopri5")
     if num_steps < 1:
         raise ValueError(f"num_steps must be >= 1, got {num_steps}")
-    flow = module.forward_flow                            # one bound method: the graph's key
-    state = {"gv": None, "key": None}
+    flow = module.forward_flow                            # one bound method: the network a kept capture is matched on
+    captures = types.SimpleNamespace()                    # this closure's capture lives here, not on the module
 
     def sample(x: torch.Tensor):
         module.eval()
         logits = module.forward_segmentation(x)
         probs = torch.softmax(logits, dim=1) if module.num_classes is not None else torch.sigmoid(logits)
-        if method == "dopri5" and not graph:
-            return dopri5_integrate(flow, _prep_source(x), atol, rtol, per_sample=True), probs.float()
-        if rk and not graph:
-            return fixed_step_integrate(flow, _prep_source(x), num_steps, method), probs.float()
-        if not graph:
-            return euler_integrate(flow, _prep_source(x), num_steps), probs.float()
-        key = (tuple(x.shape), engine.mutation_epoch[0], tuple(p._version for p in module.parameters()))
-        if state["gv"] is None or state["key"] != key:
-            if state["gv"] is not None:
-                state["gv"].close()
-            state["gv"], state["key"] = (_Dopri5Graph(flow, _prep_source(x), atol, rtol, 1000) if method == "dopri5"
-                                         else _FixedStepGraph(flow, _prep_source(x), num_steps, method) if rk
-                                         else GraphedVelocity(flow, _prep_source(x), 1.0 / num_steps)), key
-        if method == "dopri5" or rk:
-            return state["gv"].solve(_prep_source(x)), probs.float()
-        return state["gv"].solve_euler(_prep_source(x), num_steps), probs.float()
+        return solve(flow, _prep_source(x), method, num_steps, atol, rtol, graph=graph,
+                     per_sample=method == "dopri5", cache_on=captures), probs.float()
 
     return sample

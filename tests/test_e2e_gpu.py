@@ -367,3 +367,50 @@ def test_graph_captured_sampler_equals_the_eager_one(golden_tiny):
     assert not torch.equal(moved, eager) and torch.equal(moved, euler_generate(net, x, n))
     net._s2s_euler_graph.close()                                   # owned lifetime: the capture goes with its user
     assert getattr(net, "_s2s_euler_graph", None) is None
+
+
+def test_a_closed_euler_graph_no_longer_matches_and_is_captured_again(golden_tiny):
+    """``close()`` ends a capture for every holder of the object: it stops matching, so a cache that still holds it
+    captures again and never replays a released graph."""
+    from stain2stain_amd import euler_generate
+    G = golden_tiny
+    net = build_net(G, "fp32").eval()
+    x = G["euler/x_start"].to(DEV)
+    n = int(G["euler/n_steps"])
+    eager = euler_generate(net, x, n)
+    assert torch.equal(euler_generate(net, x, n, graph=True), eager)
+    g0 = net._s2s_euler_graph
+    assert g0.matches(net, x, 1.0 / n)
+    g0.close()
+    assert g0.graph is None and getattr(net, "_s2s_euler_graph", None) is None and not g0.matches(net, x, 1.0 / n)
+    object.__setattr__(net, "_s2s_euler_graph", g0)                # a cache that kept the closed object
+    assert torch.equal(euler_generate(net, x, n, graph=True), eager)
+    g1 = net._s2s_euler_graph
+    assert g1 is not g0 and g1.graph is not None and g1.matches(net, x, 1.0 / n)
+    g1.close()
+    assert getattr(net, "_s2s_euler_graph", None) is None
+
+
+def test_a_module_generate_leaves_no_live_capture_behind(golden_tiny, monkeypatch):
+    """``generate(graph=True)`` captures for one solve: with the batch-wide dopri5 and with Euler the capture is closed
+    when the solve ends, and nothing is left on the network."""
+    from stain2stain_amd import (ConditionalFlowMatchingModule, GraphedVelocity, SolverConfig, dopri5_generate,
+                                 euler_generate)
+    G = golden_tiny
+    net = build_net(G, "fp32").eval()
+    x = G["euler/x_start"].to(DEV)
+    n = int(G["euler/n_steps"])
+    made, init = [], GraphedVelocity.__init__
+
+    def spy(self, *args, **kwargs):
+        made.append(self)
+        init(self, *args, **kwargs)
+
+    want_dopri5, want_euler = dopri5_generate(net, x[:1]), euler_generate(net, x, n)
+    monkeypatch.setattr(GraphedVelocity, "__init__", spy)
+    mod = ConditionalFlowMatchingModule(net, solver=SolverConfig())
+    assert torch.equal(mod.generate(x[:1], graph=True), want_dopri5)
+    assert len(made) == 1 and made[0].graph is None
+    assert torch.equal(mod.generate(x, num_steps=n, method="euler", graph=True), want_euler)
+    assert len(made) == 2 and made[1].graph is None
+    assert getattr(net, "_s2s_euler_graph", None) is None
