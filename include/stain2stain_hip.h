@@ -345,6 +345,30 @@ int s2s_head_mse_eval_blocks(int B, int H, int W, int C);
 int s2s_head_mse_eval(int dtype, const void* x, int ldx, const float* w, const float* bias, const float* u_nchw,
                       float* loss, double* lpart, int B, int H, int W, int C, int Cout, void* stream);
 
+/* ---- image-quality metrics (image_metrics.hip) ---------------------------------------------------------
+ * Per-sample MSE, MAE, PSNR = 10 log10(L^2 / mse) (+inf at mse == 0) and SSIM (Wang et al. 2004: separable Gaussian
+ * window of `win` taps, odd, <= 11, normalised, computed by the caller: `taps` is a HOST array of win floats;
+ * C1 = (k1 L)^2, C2 = (k2 L)^2, biased local moments, only the (H - win + 1)(W - win + 1) positions per channel whose
+ * window lies inside the image), all over every channel.  One fused pass: a workgroup owns 32 x 32 valid positions and
+ * writes three fp64 partials (sum ssim, sum d^2, sum |d|) at part[((n * nby + by) * nbx + bx) * 3], by / bx the block's
+ * row / column in the whole image; part: double[B * s2s_image_quality_blocks(H, W, win) * 3].  No atomics, no host
+ * synchronisation, bit-reproducible; H, W >= win, otherwise free.
+ * s2s_image_quality_f32: float [B][C][H][W] pairs in the network's range, C <= 4; quantize 0: clamp(x * 0.5 + 0.5, 0, 1)
+ *   with L = 1, quantize 1: trunc(clamp((x * 0.5 + 0.5) * 255, 0, 255)) with L = 255 (s2s_region_finalize's uint8).
+ * s2s_image_quality_u8: uint8 [B][.][W][3] pairs, row pitches and sample strides in bytes, L = 255.  The buffers hold
+ *   image rows [band_top, band_top + band_h) of an H x W image; block rows [by0, by0 + nby) are computed, which read
+ *   image rows [32 by0, min(32 (by0 + nby) + win - 1, H)).
+ * s2s_image_quality_finalize: out: float [4][B] = psnr, ssim, mae, mse from the partials, summed in a fixed order;
+ *   `range` is L. */
+int s2s_image_quality_blocks(int H, int W, int win);
+int s2s_image_quality_f32(const float* a, const float* b, int B, int C, int H, int W, int quantize, int win,
+                          const float* taps, float k1, float k2, double* part, void* stream);
+int s2s_image_quality_u8(const void* a, long pitch_a, long img_a, const void* b, long pitch_b, long img_b, int B,
+                         int band_top, int band_h, int H, int W, int by0, int nby, int win, const float* taps, float k1,
+                         float k2, double* part, void* stream);
+int s2s_image_quality_finalize(const double* part, int B, int C, int H, int W, int win, float range, float* out,
+                               void* stream);
+
 /* ---- loss variants and class conditioning (loss_variants.hip) -- SURVEY section 8 row f4 -----------------
  * ROI-weighted MSE (conditional_flow_matching_masked.py:76-90): w = 1 + roi_lambda * mask,
  *   out[0] = sum(w (v-u)^2) / (sum(w) + 1e-8), w broadcast over C.  v, u: float[B][C][HW]; mask: float[B][HW];

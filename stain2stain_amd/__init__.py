@@ -22,6 +22,7 @@ from .ema import FusedEMA
 from .multitask_trainer import MultiTaskTrainer
 from .evaluation import EvalAccumulator
 from .region import multitask_sampler, plan_tiles, translate_region
+from .image_metrics import generation_quality, image_quality, plan_bands, region_quality
 
 __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeEmbedding", "FlowUNet",
            "ConditionalFlowMatcher", "ConditionalFlowMatchingModule", "MultiTaskFlowMatchingModule", "euler_generate", "dopri5_generate", "euler_integrate", "dopri5_integrate", "SolverConfig", "GraphedVelocity",
@@ -30,4 +31,5 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "checkpoint", "InstanceNormLeakyReLU", "Conv4x4Stride1", "Conv4x4Stride2", "ConvTranspose4x4Stride2",
            "Pix2PixGenerator", "PatchGANDiscriminator", "Pix2PixTrainer", "FusedAdam", "FusedEMA", "MultiTaskTrainer",
            "EvalAccumulator", "plan_tiles", "translate_region", "multitask_sampler", "FIXED_STEP_METHODS",
-           "fixed_step_generate", "fixed_step_integrate"]
+           "fixed_step_generate", "fixed_step_integrate", "image_quality", "region_quality", "generation_quality",
+           "plan_bands"]

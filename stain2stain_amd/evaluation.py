@@ -16,6 +16,7 @@ no running statistic, and it never waits for the device.
 from __future__ import annotations
 
 import contextlib
+import types
 from typing import Dict, Iterable, Optional
 
 import torch
@@ -53,6 +54,69 @@ def mask_logits(encoder, seg_decoder, source: torch.Tensor, encoder_training: bo
     ectx = engine.encoder_forward(encoder._blocks, source.float().contiguous(), dt, encoder_training)
     feats = ectx.feats
     return engine.decoder_forward(seg_decoder, feats[-1], feats[:-1][::-1], None, dt, decoder_training).v
+
+
+class GenerationEval:
+    """What a trainer's ``evaluate_generation`` keeps between calls: per network (live / EMA) the eval-mode velocity
+    ``f(t, x)`` and the holder its captured sampler step is cached on (``samplers._GraphedStep.cached`` matches a capture
+    on the callable's identity, so the callable has to persist).  The velocity runs the engine forward with
+    ``training=False`` -- BatchNorm from the running statistics -- whatever mode the modules are in, so no module mode
+    is touched.  A capture is rebuilt when ``engine.mutation_epoch`` moves, which every optimiser step does."""
+
+    def __init__(self):
+        self._slots = {}
+
+    def velocity(self, key, encoder, flow_decoder, time_dim: int):
+        slot = self._slots.get(key)
+        if slot is None or slot[2] is not encoder or slot[3] is not flow_decoder:
+            if slot is not None:
+                self._close(slot[1])
+
+            def f(t: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+                dt = encoder.compute_dtype
+                if t.dim() == 0 or t.shape[0] != x.shape[0]:
+                    t = t.reshape(-1)[:1].expand(x.shape[0])
+                feats = engine.encoder_forward(encoder._blocks, x.float().contiguous(), dt, False).feats
+                temb = ops.time_embedding(t.float().contiguous(), time_dim)
+                return engine.decoder_forward(flow_decoder, feats[-1], feats[:-1][::-1], temb, dt, False).v
+
+            slot = self._slots[key] = (f, types.SimpleNamespace(), encoder, flow_decoder)
+        return slot[0], slot[1]
+
+    @staticmethod
+    def _close(holder) -> None:
+        from . import samplers
+        samplers.close_cached(holder)
+
+    def holders(self):
+        """The objects the captured steps are cached on, one per network used so far."""
+        return [slot[1] for slot in self._slots.values()]
+
+    def close(self) -> None:
+        for slot in self._slots.values():
+            self._close(slot[1])
+        self._slots.clear()
+
+
+def generation_values(state: GenerationEval, key, encoder, flow_decoder, time_dim: int, x0: torch.Tensor,
+                      x1: torch.Tensor, num_steps: int, method: str, graph: bool, quantize: bool,
+                      accumulator: Optional["EvalAccumulator"]) -> Dict[str, torch.Tensor]:
+    """``x0`` carried to t = 1 by ``samplers.solve`` on the eval-mode network, scored against ``x1``
+    (``image_metrics.image_quality``): the per-sample {"psnr", "ssim", "mae", "mse"}.  ``method="dopri5"`` runs the
+    per-sample controller (``per_sample=True``, as ``region.multitask_sampler`` does), so that a sample's score does not
+    depend on its batch mates, at the default tolerances; ``num_steps`` plays no role then.  The caller sets the
+    workspace owner and the grad mode."""
+    from . import image_metrics, samplers
+    if method not in samplers.SOLVER_METHODS:
+        raise ValueError(f"method must be one of {', '.join(map(repr, samplers.SOLVER_METHODS))}, got {method!r}")
+    f, holder = state.velocity(key, encoder, flow_decoder, time_dim)
+    x = samplers._prep_source(x0)
+    pred = samplers.solve(f, x, method, num_steps, graph=graph, per_sample=method == "dopri5",
+                          cache_on=holder if graph else None)
+    values = image_metrics.image_quality(pred, x1.detach().float().contiguous(), quantize=quantize)
+    if accumulator is not None:
+        accumulator.add({k: v.mean() for k, v in values.items()}, int(x.shape[0]))
+    return values
 
 
 def segmentation_values(logits: torch.Tensor, mask: torch.Tensor, num_classes: Optional[int], ignore_index: int,

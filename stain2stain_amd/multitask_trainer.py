@@ -105,6 +105,7 @@ class MultiTaskTrainer:
         self.overlap_wgrad = True
         self._group = 0
         self._eval_owner = object()         # evaluate()'s workspaces, released by close()
+        self._generation = evaluation.GenerationEval()      # evaluate_generation()'s velocities and captured steps
         self._ema = None
         if ema_decay is not None:
             self.fp.enable_ema(ema_decay)
@@ -246,8 +247,21 @@ class MultiTaskTrainer:
             accumulator.add(out, x0.shape[0])
         return out
 
+    def evaluate_generation(self, source: torch.Tensor, target: torch.Tensor, num_steps: int = 50,
+                            method: str = "euler", graph: bool = False, use_ema: bool = False,
+                            accumulator: Optional[evaluation.EvalAccumulator] = None,
+                            quantize: bool = True) -> Dict[str, torch.Tensor]:
+        """Image quality of the flow head's generated batch against the paired ``target``: per-sample {"psnr", "ssim",
+        "mae", "mse"} (fp32 [B] device tensors), as ``CFMTrainer.evaluate_generation``.  The reference's ``generate``
+        also returns the mask; it plays no role here.  ``method="dopri5"``: the per-sample controller, as there.  Touches no training state and uses ``evaluate``'s workspaces."""
+        enc, fdec, _ = self.ema_model() if use_ema else (self.encoder, self.flow_decoder, self.seg_decoder)
+        with ops.workspace_owner(self._eval_owner), evaluation.eval_grad_mode():
+            return evaluation.generation_values(self._generation, bool(use_ema), enc, fdec, self.time_emb_dim, source,
+                                                target, num_steps, method, graph, quantize, accumulator)
+
     def close(self) -> None:
-        """Release evaluate()'s workspaces."""
+        """Release evaluate()'s workspaces and evaluate_generation()'s captured sampler steps."""
+        self._generation.close()
         ops.release_workspaces(self._eval_owner)
 
     def __del__(self):

@@ -515,6 +515,14 @@ class _Dopri5Graph(_GraphedStep):
         return self.solver.solve(source, return_stats, replay=self._replay)
 
 
+def close_cached(holder) -> None:
+    """Close every captured step ``_GraphedStep.cached`` keeps on ``holder`` (whatever kinds exist)."""
+    for kind in _GraphedStep.__subclasses__():
+        g = getattr(holder, kind.slot, None)
+        if g is not None:
+            g.close()
+
+
 def solve(f, x: torch.Tensor, method: str, num_steps: Optional[int] = None, atol: float = 1e-4, rtol: float = 1e-4,
           max_steps: int = 1000, graph: bool = False, per_sample: bool = False, return_stats: bool = False,
           cache_on=None):

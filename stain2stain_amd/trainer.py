@@ -140,6 +140,7 @@ class CFMTrainer:
             self._ema = TrainerEMA(self.fp, [net], ema_buffers)
         # evaluate()'s workspaces: never the ones a captured training step has baked into its graph (released by close())
         self._eval_owner = object()
+        self._generation = evaluation.GenerationEval()      # evaluate_generation()'s velocities and captured steps
 
     step_count = property(lambda self: self.fp.step_count)
     bucketer = property(lambda self: self.fp.bucketer)
@@ -337,10 +338,31 @@ class CFMTrainer:
             accumulator.add(out, x0.shape[0])
         return out
 
+    def evaluate_generation(self, x0: torch.Tensor, x1: torch.Tensor, num_steps: int = 50, method: str = "euler",
+                            graph: bool = False, use_ema: bool = False,
+                            accumulator: Optional[evaluation.EvalAccumulator] = None,
+                            quantize: bool = True) -> Dict[str, torch.Tensor]:
+        """Image quality of one generated batch: ``x0`` is carried to t = 1 by ``samplers.solve`` (``method`` one of
+        ``samplers.SOLVER_METHODS``, ``num_steps`` for the fixed-step ones; ``graph``: a captured step, kept until the
+        next optimiser step) on the eval-mode network and scored against the paired ``x1``.  Returns the per-sample
+        {"psnr", "ssim", "mae", "mse"} of ``image_metrics.image_quality`` (fp32 [B] device tensors; ``quantize`` as
+        there).  Like ``evaluate`` it touches no training state -- parameters, running statistics, module modes,
+        gradients, Adam moments, step count, packed weights, a captured training step -- never waits for the device
+        (eagerly; a capture does) and uses workspaces of its own.  ``accumulator``: the batch means are added with weight
+        ``x0.shape[0]``.  ``use_ema``: sample from the averaged network.  ``method="dopri5"`` runs the per-sample
+        controller at the default tolerances (a sample's score then does not depend on its batch mates; ``generate``'s
+        default is the batch-wide one) and ignores ``num_steps``."""
+        net = self.ema_model() if use_ema else self.net
+        with ops.workspace_owner(self._eval_owner), evaluation.eval_grad_mode():
+            return evaluation.generation_values(self._generation, bool(use_ema), net.encoder, net.flow_decoder,
+                                                net.time_embedding.dim, x0, x1, num_steps, method, graph, quantize,
+                                                accumulator)
+
     def close(self) -> None:
         """Drop the captured graph, its static buffers and the pinned Adam-scalar ring while torch and the HIP runtime are
         fully alive (a captured step sits in a reference cycle with its trainer; left to the cyclic collector it may be
         destroyed during another capture or at interpreter exit, in an order the runtime does not define)."""
+        self._generation.close()
         self._graph_step.close()
         ops.release_workspaces(self)
         ops.release_workspaces(self._eval_owner)
