@@ -307,6 +307,33 @@ int s2s_region_blend(const float* tiles, int c0, const float* tiles1, int c1, co
 int s2s_region_finalize(float* acc, int band_rows, int W, int C, int r0, int r1, void* out_u8, long pitch_u8,
                         float* out_f, long pitch_f, int out_top, void* stream);
 
+/* ---- tissue-aware regions: background tiles skip the sampler (region.hip) ----------
+ * All three are atomic-free with one writer per output element, so results are bit-reproducible.
+ * s2s_region_tissue_count: counts[k] (int32 [n], every entry written) = the tissue pixels of tile k's intersection
+ *   with the H x W image, one workgroup per tile; a pixel is tissue iff min(R, G, B) < white and max(R, G, B) >= black
+ *   (white in 1..256, black in 0..255; 0 disables the dark test).  img_u8, pitch, band_top, band_h and origins as in
+ *   s2s_region_gather, so a host image can be counted band by band; reflected padding is not counted.  The origins live
+ *   on the GPU, out of the host's sight: the host check covers what it can see (S2S_ERR_SHAPE), and a tile whose
+ *   in-image rows are not all inside the band reads nothing and gets counts[k] = -1.  Choose the bands so that this
+ *   does not happen.
+ * s2s_region_skip_weight: ws, a ring of band_rows rows of W floats (row r at r % band_rows), += wy(i) * wx(j) of the
+ *   n skipped tiles at origins, in order, over image rows [r0, r1) (r1 - r0 <= band_rows), with s2s_region_blend's
+ *   window.  One writer per element; reads no image bytes.
+ * s2s_region_finalize_mixed: s2s_region_finalize for a region with skipped tiles.  src_u8: the source image's rows
+ *   from image row src_top on (row pitch src_pitch bytes), covering [r0, r1).  Per pixel, with wk = acc[C]:
+ *   wk == 0 (no kept tile covers it): out_u8 = the source bytes, copied; out_f[0..2] = (u / 255 - 0.5) / 0.5,
+ *   out_f[3..] = 0.  Otherwise x_c = fmaf(ws, (u_c / 255 - 0.5) / 0.5, acc_c) / (wk + ws) for c < 3 and
+ *   acc_c / (wk + ws) for the probability channels (a skipped tile's probabilities are 0), then the save conversion of
+ *   s2s_region_finalize.  Both ring rows are cleared.  With ws == 0 everywhere it is bit-equal to s2s_region_finalize.
+ *   3 <= C <= 8. */
+int s2s_region_tissue_count(const void* img_u8, long pitch, int H, int W, int band_top, int band_h, const int* origins,
+                            int n, int T, int white, int black, int* counts, void* stream);
+int s2s_region_skip_weight(const int* origins, int n, int T, int overlap, float* ws, int band_rows, int H, int W,
+                           int r0, int r1, void* stream);
+int s2s_region_finalize_mixed(float* acc, float* ws, int band_rows, int W, int C, int r0, int r1, const void* src_u8,
+                              long src_pitch, int src_top, void* out_u8, long pitch_u8, float* out_f, long pitch_f,
+                              int out_top, void* stream);
+
 /* ---- segmentation loss (seg_loss.hip) -- SURVEY section 8 row f2 --------------------------------------
  * seg = dw * DiceLoss(sigmoid(z), g) + (1-dw) * BCEWithLogits(z, g)  (conditional_flow_matching_multitask.py:36-53,
  * 174-202).  z, g: float[n]; out: float[3] = {seg, dice, bce}; dz (optional) = grad_scale * d seg / dz;

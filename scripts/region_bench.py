@@ -5,7 +5,11 @@
   * the gather / blend / finalise kernels' times per region call from a separate run of this script under
     `rocprofv3 --kernel-trace --stats` (a child process), with their achieved GB/s against algorithmic bytes.
 Settings: default FlowUNet in bf16, a synthetic uint8 region, tile 256, overlap 32, batch 32, 50 Euler steps as a
-graph.  Usage: python scripts/region_bench.py [--size 4096] [--repeat 3] [--no-profile] [--out-dir DIR]"""
+graph.  --min-tissue F runs the call with ``min_tissue=F`` (background tiles skip the sampler) and
+--background FRACTION makes that share of the region's rows glass (bytes >= --white; implies --min-tissue 0.5); the
+line then also holds kept, skipped and sampler_calls, and the kernel table the tissue count, the skip weights and the
+mixed finalise.  Usage: python scripts/region_bench.py [--size 4096] [--repeat 3] [--no-profile] [--out-dir DIR]
+[--background FRACTION] [--min-tissue F] [--white 220]"""
 import argparse
 import csv
 import glob
@@ -20,8 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 
-from stain2stain_amd import FlowUNet, euler_generate, translate_region
-from stain2stain_amd.region import plan_tiles
+from stain2stain_amd import FlowUNet, euler_generate, plan_region_batches, tissue_counts, translate_region
+from stain2stain_amd.region import band_rows_for, plan_tiles
 
 DEV = "cuda:0"
 KERNELS = ("region_gather_kernel", "region_blend_kernel", "region_finalize_kernel")
@@ -44,11 +48,46 @@ def algorithmic_bytes(H, W, tile, overlap, batch, C=3):
     return dict(zip(KERNELS, (gather, blend, finalize)))
 
 
+SKIP_KERNELS = ("region_gather_kernel", "region_blend_kernel", "region_tissue_count_kernel",
+                "region_skip_weight_kernel", "region_finalize_mixed_kernel")
+
+
+def algorithmic_bytes_skipping(H, W, tile, overlap, batch, keep, C=3):
+    """The same for a call with ``min_tissue``: gather and blend move the kept tiles only (padded sampler calls
+    included); the count reads every tile's pixels once; the skip weights read and write the weight-ring rows of every
+    range with a skipped tile; the mixed finalise reads both rings and the source, writes the uint8 image and clears
+    both rings."""
+    plan = plan_tiles(H, W, tile, overlap)
+    tops = plan[:, 0].tolist()
+    kept = keep.tolist()
+    gather = blend = skip = 0
+    for p0, p1 in plan_region_batches(plan, keep, batch, band_rows_for(H, W, tile, overlap, batch), tile):
+        rows = min(H, tops[p1 - 1] + tile) - tops[p0]
+        nk = sum(kept[p0:p1])
+        if nk:
+            gather += batch * tile * tile * 3 * (1 + 4)
+            blend += nk * C * tile * tile * 4 + 2 * rows * W * (C + 1) * 4
+        if nk < p1 - p0:
+            skip += 2 * rows * W * 4
+    count = sum(min(tile, H - y) * min(tile, W - x) * 3 for y, x in plan.tolist()) + 4 * len(tops)
+    finalize = H * W * ((C + 1) * 4 * 2 + 4 * 2 + 3 + 3)
+    return dict(zip(SKIP_KERNELS, (gather, blend, count, skip, finalize)))
+
+
+def make_image(args):
+    g = torch.Generator(device=DEV).manual_seed(1984)
+    img = torch.randint(0, 256, (args.size, args.size, 3), generator=g, dtype=torch.uint8, device=DEV)
+    glass = round(args.background * args.size)
+    if glass:                                              # the lower rows are glass: bytes in [white, 255]
+        img[args.size - glass:] = torch.randint(args.white, 256, (glass, args.size, 3), generator=g, dtype=torch.uint8,
+                                                device=DEV)
+    return img
+
+
 def run(args):
     torch.manual_seed(1984)
     net = FlowUNet(precision="bf16").to(DEV).eval()
-    g = torch.Generator(device=DEV).manual_seed(1984)
-    img = torch.randint(0, 256, (args.size, args.size, 3), generator=g, dtype=torch.uint8, device=DEV)
+    img = make_image(args)
     spans = []
 
     def sampler(x):
@@ -60,6 +99,8 @@ def run(args):
         return out
 
     kw = dict(tile=args.tile, overlap=args.overlap, batch=args.batch)
+    if args.min_tissue is not None:
+        kw.update(min_tissue=args.min_tissue, white=args.white)
     translate_region(img, sampler, **kw)                   # warm-up: captures the graph, loads every kernel
     torch.cuda.synchronize()
     walls, samp = [], []
@@ -81,7 +122,9 @@ def profile(args):
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "region", "--",
            sys.executable, os.path.abspath(__file__), "--inner", "--repeat", "1", "--size", str(args.size),
            "--tile", str(args.tile), "--overlap", str(args.overlap), "--batch", str(args.batch),
-           "--steps", str(args.steps)]
+           "--steps", str(args.steps), "--background", str(args.background), "--white", str(args.white)]
+    if args.min_tissue is not None:
+        cmd += ["--min-tissue", str(args.min_tissue)]
     rc = subprocess.run(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=args.profile_timeout)
     if rc.returncode != 0:
         raise RuntimeError(f"rocprofv3 run failed ({rc.returncode}): {rc.stderr.decode()[-2000:]}")
@@ -89,15 +132,21 @@ def profile(args):
     if not files:
         raise RuntimeError(f"no region_kernel_stats.csv under {out}")
     calls_per_run = 2                                      # the warm-up call and the timed one
-    nbytes = algorithmic_bytes(args.size, args.size, args.tile, args.overlap, args.batch)
+    if args.min_tissue is None:
+        names, nbytes = KERNELS, algorithmic_bytes(args.size, args.size, args.tile, args.overlap, args.batch)
+    else:
+        counts, areas = tissue_counts(make_image(args), args.tile, args.overlap, white=args.white)
+        keep = torch.tensor([c >= args.min_tissue * a for c, a in zip(counts.tolist(), areas.tolist())])
+        nbytes = algorithmic_bytes_skipping(args.size, args.size, args.tile, args.overlap, args.batch, keep)
+        names = tuple(k for k in SKIP_KERNELS if nbytes[k])  # no launch without a kept / a skipped tile
     res = {}
     for row in csv.DictReader(open(files[0])):
-        for k in KERNELS:
+        for k in names:
             if k in row["Name"]:
                 r = res.setdefault(k, {"launches": 0, "ns": 0.0})
                 r["launches"] += int(row["Calls"])
                 r["ns"] += float(row["TotalDurationNs"])
-    for k in KERNELS:
+    for k in names:
         if k not in res:
             raise RuntimeError(f"{k} missing from the kernel statistics")
         r = res[k]
@@ -115,11 +164,18 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--background", type=float, default=0.0, help="share of the region's rows that is glass")
+    ap.add_argument("--min-tissue", type=float, default=None, help="run with min_tissue (default 0.5 with --background)")
+    ap.add_argument("--white", type=int, default=220)
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--profile-timeout", type=int, default=300)
     ap.add_argument("--out-dir", default=None, help="where the rocprofv3 output goes (default: a new temporary directory)")
     ap.add_argument("--inner", action="store_true", help=argparse.SUPPRESS)   # the child under rocprofv3
     args = ap.parse_args()
+    if not 0.0 <= args.background <= 1.0:
+        raise SystemExit("region_bench: --background must lie in [0, 1]")
+    if args.background and args.min_tissue is None:
+        args.min_tissue = 0.5
     if not torch.cuda.is_available():
         raise SystemExit("region_bench: needs a GPU")
     if args.inner:
@@ -134,7 +190,9 @@ def main():
     mpix = args.size * args.size / 1e6
     line = {"metric": "region_translate", "size": args.size, "tile": args.tile, "overlap": args.overlap,
             "batch": args.batch, "euler_steps": args.steps, "precision": "bf16", "tiles": st["tiles"],
-            "batches": st["batches"], "band_rows": st["band_rows"],
+            "batches": st["batches"], "band_rows": st["band_rows"], "background": args.background,
+            "min_tissue": args.min_tissue, "kept": st["kept"], "skipped": st["skipped"],
+            "sampler_calls": st["sampler_calls"],
             "accumulator_MB": round(st["accumulator_bytes"] / 1e6, 1),
             "wall_s": round(wall, 4), "wall_s_each": [round(w, 4) for w in walls], "MPix_s": round(mpix / wall, 3),
             "sampler_s": round(s, 4), "outside_sampler_s": round(wall - s, 4),

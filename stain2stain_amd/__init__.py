@@ -21,7 +21,7 @@ from .optim import FusedAdam
 from .ema import FusedEMA
 from .multitask_trainer import MultiTaskTrainer
 from .evaluation import EvalAccumulator
-from .region import multitask_sampler, plan_tiles, translate_region
+from .region import multitask_sampler, plan_region_batches, plan_tiles, tissue_counts, translate_region
 from .image_metrics import generation_quality, image_quality, plan_bands, region_quality
 
 __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeEmbedding", "FlowUNet",
@@ -30,6 +30,6 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "MaskConditionedFlowMatchingModule", "ROICharbonnierFlowMatchingModule", "ROIWeightedFlowMatchingModule",
            "checkpoint", "InstanceNormLeakyReLU", "Conv4x4Stride1", "Conv4x4Stride2", "ConvTranspose4x4Stride2",
            "Pix2PixGenerator", "PatchGANDiscriminator", "Pix2PixTrainer", "FusedAdam", "FusedEMA", "MultiTaskTrainer",
-           "EvalAccumulator", "plan_tiles", "translate_region", "multitask_sampler", "FIXED_STEP_METHODS",
+           "EvalAccumulator", "plan_tiles", "translate_region", "tissue_counts", "plan_region_batches", "multitask_sampler", "FIXED_STEP_METHODS",
            "fixed_step_generate", "fixed_step_integrate", "image_quality", "region_quality", "generation_quality",
            "plan_bands"]

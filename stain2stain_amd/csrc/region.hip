@@ -182,6 +182,128 @@ __global__ void region_finalize_kernel(float* __restrict__ acc, int band_rows, i
   }
 }
 
+// ---- tissue-aware regions: background tiles are measured, skipped and passed through --------
+
+__device__ __forceinline__ int is_tissue(unsigned r, unsigned g, unsigned b, int white, int black) {
+  const int mn = (int)min(r, min(g, b)), mx = (int)max(r, max(g, b));
+  return (mn < white && mx >= black) ? 1 : 0;
+}
+
+// One workgroup of 256 lanes per tile; counts[k] = tissue pixels of the tile's intersection with the image (reflected
+// padding is not counted).  Lanes walk the in-image rows as the gather does: one lane per 4 consecutive pixels, three
+// dword loads when the 12 bytes are aligned and the quad is whole, bytes otherwise.  Integer count per lane, xor-shuffle
+// over the wave, four partials through LDS, one plain store: every counts[k] is written.  A tile whose in-image rows are
+// not all inside the band gets -1 and reads nothing.
+__global__ void __launch_bounds__(256)
+region_tissue_count_kernel(const unsigned char* __restrict__ img, long pitch, int H, int W, int band_top, int band_h,
+                           const int* __restrict__ origins, int T, int white, int black, int* __restrict__ counts) {
+  __shared__ int part[4];
+  const int k = blockIdx.x;
+  const int top = origins[2 * k], left = origins[2 * k + 1];
+  const int hh = min(T, H - top), ww = min(T, W - left);
+  if (top < band_top || top + hh > band_top + band_h || top < 0 || left < 0 || hh <= 0 || ww <= 0) {   // block-uniform
+    if (threadIdx.x == 0) counts[k] = -1;
+    return;
+  }
+  const int nq = (ww + 3) >> 2;
+  const int total = hh * nq;
+  int cnt = 0;
+  for (int q = threadIdx.x; q < total; q += 256) {
+    const int y = q / nq, xq = q - y * nq;
+    const unsigned char* p = img + (long)(top - band_top + y) * pitch + 3L * (left + 4 * xq);
+    const int px = min(4, ww - 4 * xq);
+    if (px == 4 && ((uintptr_t)p & 3) == 0) {
+      const unsigned w0 = reinterpret_cast<const unsigned*>(p)[0];   // r0 g0 b0 r1
+      const unsigned w1 = reinterpret_cast<const unsigned*>(p)[1];   // g1 b1 r2 g2
+      const unsigned w2 = reinterpret_cast<const unsigned*>(p)[2];   // b2 r3 g3 b3
+      cnt += is_tissue(w0 & 255, (w0 >> 8) & 255, (w0 >> 16) & 255, white, black);
+      cnt += is_tissue(w0 >> 24, w1 & 255, (w1 >> 8) & 255, white, black);
+      cnt += is_tissue((w1 >> 16) & 255, w1 >> 24, w2 & 255, white, black);
+      cnt += is_tissue((w2 >> 8) & 255, (w2 >> 16) & 255, w2 >> 24, white, black);
+    } else {
+      for (int j = 0; j < px; ++j) cnt += is_tissue(p[3 * j], p[3 * j + 1], p[3 * j + 2], white, black);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) counts[k] = part[0] + part[1] + part[2] + part[3];
+}
+
+// One thread per image pixel of rows [r0, r0 + rows), the single writer of that pixel's skip weight: ws += wy(i) * wx(j)
+// for every skipped tile covering it, in the given order, with the blend's axis_weight.  Reads no image bytes.
+__global__ void region_skip_weight_kernel(const int* __restrict__ origins, int n, int T, int overlap,
+                                          float* __restrict__ ws, int band_rows, int W, int r0, int wblocks) {
+  const int r = r0 + (int)(blockIdx.x / wblocks);
+  const int x = (int)(blockIdx.x % wblocks) * blockDim.x + threadIdx.x;
+  if (x >= W) return;
+  float* p = ws + (long)(r % band_rows) * W + x;
+  float v = *p;
+  bool hit = false;
+  for (int k = 0; k < n; ++k) {
+    const int i = r - origins[2 * k], j = x - origins[2 * k + 1];
+    if ((unsigned)i >= (unsigned)T || (unsigned)j >= (unsigned)T) continue;
+    v += axis_weight(i, T, overlap) * axis_weight(j, T, overlap);
+    hit = true;
+  }
+  if (hit) *p = v;
+}
+
+// region_finalize_kernel for a region with skipped tiles.  wk = acc[C] is the weight of the kept tiles, s = ws the
+// weight of the skipped ones, whose image is the normalised source and whose probabilities are 0.  A pixel no kept tile
+// covers is the source itself: its bytes are copied, never converted (the fp32 normalise -> save round trip loses 1 on
+// 63 of the 256 byte values).  Elsewhere x = fmaf(s, normalise_u8(src), acc) / (wk + s); with s == 0 that is acc / wk,
+// bit-equal to region_finalize_kernel.  Both ring rows are cleared.
+template <int C>
+__global__ void region_finalize_mixed_kernel(float* __restrict__ acc, float* __restrict__ ws, int band_rows, int W,
+                                             int r0, int rows, const unsigned char* __restrict__ src, long src_pitch,
+                                             int src_top, unsigned char* __restrict__ out_u8, long pitch_u8,
+                                             float* __restrict__ out_f, long pitch_f, int out_top) {
+#pragma clang fp contract(off)
+  const long total = (long)rows * W;
+  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+    const int x = (int)(q % W);
+    const int r = r0 + (int)(q / W);
+    const long ring = (long)(r % band_rows) * W + x;
+    float* p = acc + ring * (C + 1);
+    float v[C + 1];
+    load_px<C + 1>(p, v);
+    const float s = ws[ring];
+    const unsigned char* u = src + (long)(r - src_top) * src_pitch + 3L * x;
+    const unsigned char b[3] = {u[0], u[1], u[2]};
+    const bool copy = v[C] == 0.0f;
+    float o[C];
+    if (copy) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) o[c] = c < 3 ? normalise_u8(b[c]) : 0.0f;
+    } else {
+      const float den = v[C] + s;
+#pragma unroll
+      for (int c = 0; c < C; ++c) o[c] = (c < 3 ? fmaf(s, normalise_u8(b[c]), v[c]) : v[c]) / den;
+    }
+    if (out_f) {
+      float* d = out_f + (long)(r - out_top) * pitch_f + (long)x * C;
+#pragma unroll
+      for (int c = 0; c < C; ++c) d[c] = o[c];
+    }
+    if (out_u8) {
+      unsigned char* d = out_u8 + (long)(r - out_top) * pitch_u8 + 3L * x;
+#pragma unroll
+      for (int c = 0; c < 3 && c < C; ++c) {
+        const float y = o[c] * 0.5f;
+        const float z = (y + 0.5f) * 255.0f;
+        d[c] = copy ? b[c] : (unsigned char)(int)fminf(fmaxf(z, 0.0f), 255.0f);
+      }
+    }
+    float zero[C + 1];
+#pragma unroll
+    for (int c = 0; c <= C; ++c) zero[c] = 0.0f;
+    store_px<C + 1>(p, zero);
+    ws[ring] = 0.0f;
+  }
+}
+
 inline int grid_for(long total) {
   long g = (total + 255) / 256;
   if (g > 16384) g = 16384;
@@ -253,6 +375,55 @@ extern "C" int s2s_region_finalize(float* acc, int band_rows, int W, int C, int 
                      r1 - r0, (unsigned char*)out_u8, pitch_u8, out_f, pitch_f, out_top)
   S2S_REGION_SWITCH(C, S2S_FINALIZE)
 #undef S2S_FINALIZE
+  S2S_LAUNCH_CHECK();
+  return S2S_OK;
+}
+
+extern "C" int s2s_region_tissue_count(const void* img_u8, long pitch, int H, int W, int band_top, int band_h,
+                                       const int* origins, int n, int T, int white, int black, int* counts,
+                                       void* stream) {
+  if (!img_u8 || !origins || !counts) return S2S_ERR_NULL;
+  if (H <= 0 || W <= 0 || n <= 0 || T <= 0 || band_h <= 0 || band_top < 0 || band_top + band_h > H ||
+      pitch < 3L * W || white < 1 || white > 256 || black < 0 || black > 255)
+    return S2S_ERR_SHAPE;
+  hipLaunchKernelGGL(region_tissue_count_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned char*)img_u8, pitch, H, W, band_top, band_h, origins, T, white, black, counts);
+  S2S_LAUNCH_CHECK();
+  return S2S_OK;
+}
+
+extern "C" int s2s_region_skip_weight(const int* origins, int n, int T, int overlap, float* ws, int band_rows, int H,
+                                      int W, int r0, int r1, void* stream) {
+  if (!origins || !ws) return S2S_ERR_NULL;
+  if (n <= 0 || T <= 0 || overlap < 0 || overlap >= T || H <= 0 || W <= 0 || band_rows <= 0 || r0 < 0 || r1 > H ||
+      r1 <= r0 || r1 - r0 > band_rows)
+    return S2S_ERR_SHAPE;
+  const int wblocks = cdiv(W, 256);
+  const long blocks = (long)wblocks * (r1 - r0);
+  if (blocks >= (1L << 31)) return S2S_ERR_SHAPE;
+  hipLaunchKernelGGL(region_skip_weight_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, origins, n,
+                     T, overlap, ws, band_rows, W, r0, wblocks);
+  S2S_LAUNCH_CHECK();
+  return S2S_OK;
+}
+
+extern "C" int s2s_region_finalize_mixed(float* acc, float* ws, int band_rows, int W, int C, int r0, int r1,
+                                         const void* src_u8, long src_pitch, int src_top, void* out_u8, long pitch_u8,
+                                         float* out_f, long pitch_f, int out_top, void* stream) {
+  if (!acc || !ws || !src_u8 || (!out_u8 && !out_f)) return S2S_ERR_NULL;
+  if (C < 3 || C > 8 || W <= 0 || band_rows <= 0 || r0 < 0 || r1 <= r0 || r1 - r0 > band_rows || out_top < 0 ||
+      out_top > r0 || src_top < 0 || src_top > r0 || src_pitch < 3L * W || (out_u8 && pitch_u8 < 3L * W) ||
+      (out_f && pitch_f < (long)C * W))
+    return S2S_ERR_SHAPE;
+  if ((C + 1) % 4 == 0 && ((uintptr_t)acc & 15)) return S2S_ERR_ALIGN;
+  const long total = (long)(r1 - r0) * W;
+  hipStream_t s = (hipStream_t)stream;
+#define S2S_FINALIZE_MIXED(CC)                                                                                      \
+  hipLaunchKernelGGL(region_finalize_mixed_kernel<CC>, dim3(grid_for(total)), dim3(256), 0, s, acc, ws, band_rows,  \
+                     W, r0, r1 - r0, (const unsigned char*)src_u8, src_pitch, src_top, (unsigned char*)out_u8,      \
+                     pitch_u8, out_f, pitch_f, out_top)
+  S2S_REGION_SWITCH(C, S2S_FINALIZE_MIXED)
+#undef S2S_FINALIZE_MIXED
   S2S_LAUNCH_CHECK();
   return S2S_OK;
 }

@@ -1912,3 +1912,66 @@ def region_finalize(acc: torch.Tensor, r0: int, r1: int, out_u8: Optional[torch.
     rc = _L().s2s_region_finalize(_f32(acc), int(band_rows), int(W), int(C1 - 1), int(r0), int(r1), pu8, int(pitch_u8),
                                   pf, int(pitch_f), int(out_top), _stream())
     _native.check(rc, "region_finalize")
+
+
+def region_tissue_count(band: torch.Tensor, band_top: int, H: int, W: int, origins: torch.Tensor, tile: int,
+                        white: int, black: int, counts: torch.Tensor) -> torch.Tensor:
+    """counts[k] = the pixels of tile k's intersection with the H x W image for which min(R, G, B) < white and
+    max(R, G, B) >= black (int32 [n], every entry written); ``band`` as in ``region_gather``.  A tile whose in-image
+    rows are not all inside the band gets -1."""
+    ptr, pitch = _u8_rows(band)
+    n = origins.shape[0]
+    if (origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 2 or not origins.is_cuda
+            or not origins.is_contiguous()):
+        raise RuntimeError("stain2stain_amd: region_tissue_count origins must be contiguous int32 [n, 2] on the GPU")
+    if band.shape[1] != W:
+        raise RuntimeError("stain2stain_amd: region_tissue_count band width mismatch")
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (n,) or not counts.is_cuda or not counts.is_contiguous():
+        raise RuntimeError("stain2stain_amd: region_tissue_count counts must be contiguous int32 [n] on the GPU")
+    rc = _L().s2s_region_tissue_count(ptr, pitch, int(H), int(W), int(band_top), int(band.shape[0]),
+                                      origins.data_ptr(), int(n), int(tile), int(white), int(black),
+                                      counts.data_ptr(), _stream())
+    _native.check(rc, "region_tissue_count")
+    return counts
+
+
+def region_skip_weight(origins: torch.Tensor, tile: int, overlap: int, ws: torch.Tensor, H: int, r0: int,
+                       r1: int) -> None:
+    """ws (+)= the feathered window of the skipped tiles at origins[k], in order, over image rows [r0, r1) of the ring
+    ``ws`` (fp32 [band_rows, W])."""
+    if (origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 2 or not origins.is_cuda
+            or not origins.is_contiguous()):
+        raise RuntimeError("stain2stain_amd: region_skip_weight origins must be contiguous int32 [n, 2] on the GPU")
+    if ws.dim() != 2 or not ws.is_contiguous():
+        raise RuntimeError("stain2stain_amd: region_skip_weight ring must be contiguous fp32 [band_rows, W]")
+    band_rows, W = ws.shape
+    rc = _L().s2s_region_skip_weight(origins.data_ptr(), int(origins.shape[0]), int(tile), int(overlap), _f32(ws),
+                                     int(band_rows), int(H), int(W), int(r0), int(r1), _stream())
+    _native.check(rc, "region_skip_weight")
+
+
+def region_finalize_mixed(acc: torch.Tensor, ws: torch.Tensor, r0: int, r1: int, src: torch.Tensor, src_top: int,
+                          out_u8: Optional[torch.Tensor], out_f: Optional[torch.Tensor], out_top: int) -> None:
+    """``region_finalize`` for a region with skipped tiles: ``ws`` (fp32 [band_rows, W]) holds their window weights and
+    ``src`` the source image's rows from ``src_top`` on.  Pixels no kept tile covers are the source bytes, copied; the
+    others blend the normalised source with weight ws.  Both rings' rows are cleared."""
+    band_rows, W, C1 = acc.shape
+    if tuple(ws.shape) != (band_rows, W) or not ws.is_contiguous():
+        raise RuntimeError("stain2stain_amd: region_finalize_mixed weight ring shape mismatch")
+    psrc, src_pitch = _u8_rows(src)
+    if src.shape[1] != W or src_top > r0 or src.shape[0] < r1 - src_top:
+        raise RuntimeError("stain2stain_amd: region_finalize_mixed source rows do not cover [r0, r1)")
+    pu8, pitch_u8, pf, pitch_f = 0, 0, 0, 0
+    if out_u8 is not None:
+        pu8, pitch_u8 = _u8_rows(out_u8)
+        if out_u8.shape[1] != W or out_u8.shape[0] < r1 - out_top:
+            raise RuntimeError("stain2stain_amd: region_finalize_mixed uint8 output too small")
+    if out_f is not None:
+        if (not out_f.is_cuda or out_f.dtype != torch.float32 or out_f.dim() != 3 or tuple(out_f.shape[1:]) != (W, C1 - 1)
+                or out_f.stride(2) != 1 or out_f.stride(1) != C1 - 1 or out_f.shape[0] < r1 - out_top):
+            raise RuntimeError("stain2stain_amd: region_finalize_mixed fp32 output must be [rows, W, C] with contiguous rows")
+        pf, pitch_f = out_f.data_ptr(), out_f.stride(0)
+    rc = _L().s2s_region_finalize_mixed(_f32(acc), _f32(ws), int(band_rows), int(W), int(C1 - 1), int(r0), int(r1),
+                                        psrc, int(src_pitch), int(src_top), pu8, int(pitch_u8), pf, int(pitch_f),
+                                        int(out_top), _stream())
+    _native.check(rc, "region_finalize_mixed")

@@ -68,7 +68,9 @@ def _check_output(out, batch: int, tile: int, device: torch.device, what: str, c
 
 @torch.no_grad()
 def translate_region(image: torch.Tensor, sampler: Callable, *, tile: int = 256, overlap: int = 32, batch: int = 32,
-                     return_float: bool = False):
+                     return_float: bool = False, min_tissue: Optional[float] = None,
+                     keep: Optional[torch.Tensor] = None, white: int = 220, black: int = 0,
+                     mask_channels: Optional[int] = None):
     """Translate a whole uint8 RGB region tile by tile and blend the tiles without seams.
 
     ``image``: uint8 [H, W, 3] on the GPU or the host, any row pitch (a crop view of a larger slide array works without
@@ -94,7 +96,17 @@ def translate_region(image: torch.Tensor, sampler: Callable, *, tile: int = 256,
 
     Working memory on the GPU does not grow with H: the accumulator ring holds ``band_rows`` image rows, and a host
     image is staged in and out through one pinned buffer of that height per direction.  ``translate_region.last_stats``
-    describes the last call: tiles, batches, band_rows, accumulator_bytes, channels."""
+    describes the last call: tiles, batches, band_rows, accumulator_bytes, channels, kept, skipped, sampler_calls.
+
+    Background tiles can skip the sampler.  ``min_tissue``: a fraction in [0, 1]; tile n is kept
+    iff ``counts[n] >= min_tissue * areas[n]`` with ``tissue_counts(image, tile, overlap, white=white, black=black)``
+    (a pixel is tissue iff ``min(R, G, B) < white and max(R, G, B) >= black``); the counts are copied to the host once.
+    ``keep``: the caller's own bool [N] mask in plan order instead (from a thumbnail, say); the two exclude each other,
+    and with both None nothing is skipped.  The kept tiles are compacted into sampler calls of exactly ``batch`` tiles
+    (``plan_region_batches``); a pixel no kept tile covers is the source pixel, its bytes copied (and probability 0);
+    where kept and skipped tiles overlap, the skipped ones enter the blend as the normalised source, so there are no
+    seams.  The output channels must then be known before the first sampler call: ``mask_channels`` is the sampler's
+    number of probability channels (default: its ``mask_channels`` attribute, which ``multitask_sampler`` sets, else 0)."""
     if not isinstance(image, torch.Tensor):
         raise TypeError(f"translate_region: image must be a torch.Tensor, got {type(image).__name__}")
     if image.dtype != torch.uint8:
@@ -110,6 +122,9 @@ def translate_region(image: torch.Tensor, sampler: Callable, *, tile: int = 256,
     plan = plan_tiles(H, W, tile, overlap)
     if tile % 4:
         raise ValueError(f"tile must be a multiple of 4, got {tile}")
+    if min_tissue is not None or keep is not None:
+        return _translate_skipping(image, sampler, plan, tile, overlap, batch, return_float, min_tissue, keep, white,
+                                   black, mask_channels)
     on_gpu = image.is_cuda
     dev = image.device if on_gpu else torch.device("cuda", torch.cuda.current_device())
     N = plan.shape[0]
@@ -195,7 +210,8 @@ def translate_region(image: torch.Tensor, sampler: Callable, *, tile: int = 256,
     if pending is not None:
         drain()
     translate_region.last_stats = {"tiles": N, "batches": nb, "band_rows": band_rows,
-                                   "accumulator_bytes": acc.numel() * acc.element_size(), "channels": C}
+                                   "accumulator_bytes": acc.numel() * acc.element_size(), "channels": C,
+                                   "kept": N, "skipped": 0, "sampler_calls": nb}
     extra = []
     if Cm:
         extra.append(res_f[..., 3:])
@@ -205,6 +221,254 @@ def translate_region(image: torch.Tensor, sampler: Callable, *, tile: int = 256,
 
 
 translate_region.last_stats: Optional[Dict[str, int]] = None
+
+
+# ---- tissue-aware regions: background tiles skip the sampler --------------------------------
+def _check_image(image, who: str):
+    if not isinstance(image, torch.Tensor):
+        raise TypeError(f"{who}: image must be a torch.Tensor, got {type(image).__name__}")
+    if image.dtype != torch.uint8:
+        raise ValueError(f"{who}: image must be uint8, got {image.dtype}")
+    if image.dim() != 3 or image.shape[2] != 3:
+        raise ValueError(f"{who}: image must be [H, W, 3] RGB, got {list(image.shape)}")
+    H, W = int(image.shape[0]), int(image.shape[1])
+    if image.stride(2) != 1 or (W > 1 and image.stride(1) != 3):
+        raise ValueError(f"{who}: pixels within a row must be contiguous")
+    return H, W
+
+
+def _check_thresholds(white, black):
+    white, black = operator.index(white), operator.index(black)
+    if not 1 <= white <= 256:
+        raise ValueError(f"white must lie in 1..256, got {white}")
+    if not 0 <= black <= 255:
+        raise ValueError(f"black must lie in 0..255, got {black}")
+    return white, black
+
+
+def _count_tissue(image, plan, origins, tile, white, black, dev, stage_in=None, band_in=None):
+    """int32 [N] tissue counts on the GPU.  A GPU image takes one launch; a host image streams once through the pinned
+    buffer ``stage_in`` and its GPU twin ``band_in`` (at least min(H, tile) rows each), one tile row of the plan per band."""
+    H, W = int(image.shape[0]), int(image.shape[1])
+    N = plan.shape[0]
+    counts = torch.empty((N,), dtype=torch.int32, device=dev)
+    if image.is_cuda:
+        ops.region_tissue_count(image, 0, H, W, origins[:N], tile, white, black, counts)
+        return counts
+    rows = min(H, tile)
+    if stage_in is None:
+        stage_in = torch.empty((rows, W, 3), dtype=torch.uint8, pin_memory=True)
+        band_in = torch.empty((rows, W, 3), dtype=torch.uint8, device=dev)
+    tops = plan[:, 0].tolist()
+    in_ready = None
+    p0 = 0
+    while p0 < N:
+        p1 = p0 + 1
+        while p1 < N and tops[p1] == tops[p0]:
+            p1 += 1
+        r0, r1 = tops[p0], min(H, tops[p0] + tile)
+        if in_ready is not None:
+            in_ready.synchronize()                        # the previous upload has left stage_in
+        stage_in[:r1 - r0].copy_(image[r0:r1])
+        band_in[:r1 - r0].copy_(stage_in[:r1 - r0], non_blocking=True)
+        in_ready = torch.cuda.Event()
+        in_ready.record()
+        ops.region_tissue_count(band_in[:r1 - r0], r0, H, W, origins[p0:p1], tile, white, black, counts[p0:p1])
+        p0 = p1
+    in_ready.synchronize()                                # stage_in is the caller's again
+    return counts
+
+
+def _tile_areas(plan: torch.Tensor, H: int, W: int, tile: int) -> torch.Tensor:
+    return ((plan[:, 0] + tile).clamp(max=H) - plan[:, 0]) * ((plan[:, 1] + tile).clamp(max=W) - plan[:, 1])
+
+
+@torch.no_grad()
+def tissue_counts(image: torch.Tensor, tile: int = 256, overlap: int = 32, *, white: int = 220, black: int = 0):
+    """Tissue pixels per tile of ``plan_tiles(H, W, tile, overlap)``: (counts int32 [N] on the GPU, areas int32 [N] on
+    the host).  A pixel is tissue iff ``min(R, G, B) < white and max(R, G, B) >= black`` (integer, exact); ``white`` in
+    1..256, ``black`` in 0..255, 0 disabling the dark test.  A tile's area is its intersection with the image: the
+    reflected padding of a region smaller than a tile is not counted.  ``image`` as for ``translate_region``; a host
+    image is streamed once through a pinned buffer, one tile row of the plan per band."""
+    H, W = _check_image(image, "tissue_counts")
+    white, black = _check_thresholds(white, black)
+    plan = plan_tiles(H, W, tile, overlap)
+    dev = image.device if image.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    return _count_tissue(image, plan, plan.to(dev), tile, white, black, dev), _tile_areas(plan, H, W, tile)
+
+
+def plan_region_batches(plan: torch.Tensor, keep: torch.Tensor, batch: int, band_rows: int, tile: int):
+    """Cut the plan into contiguous ranges ``[p0, p1)`` for a region whose tiles with ``keep[n]`` false skip the
+    sampler: a list of (p0, p1) that partitions [0, N) in order.  Greedy: each range is the longest that holds at most
+    ``batch`` kept tiles and spans at most ``band_rows`` image rows, ``tops[p1 - 1] + tile - tops[p0] <= band_rows``, so
+    it fits the accumulator ring.  (Tiles of the first tile's own row always fit: they span the same rows, which matters
+    only for a region lower than a tile, where ``band_rows`` = H < tile.)  With ``keep`` all true the ranges are the
+    fixed ``batch``-sized slices, whose span ``band_rows_for`` bounds.  Host only."""
+    batch, band_rows, tile = operator.index(batch), operator.index(band_rows), operator.index(tile)
+    if batch < 1:
+        raise ValueError(f"batch must be >= 1, got {batch}")
+    if band_rows < 1 or tile < 1:
+        raise ValueError(f"band_rows and tile must be >= 1, got {band_rows} and {tile}")
+    if not isinstance(plan, torch.Tensor) or plan.dim() != 2 or plan.shape[1] != 2:
+        raise ValueError("plan must be the [N, 2] tensor of plan_tiles")
+    N = plan.shape[0]
+    if not isinstance(keep, torch.Tensor):
+        raise TypeError(f"keep must be a bool tensor, got {type(keep).__name__}")
+    if keep.dtype != torch.bool:
+        raise ValueError(f"keep must be a bool tensor, got {keep.dtype}")
+    if tuple(keep.shape) != (N,):
+        raise ValueError(f"keep must have shape [{N}] (one entry per tile, plan order), got {list(keep.shape)}")
+    tops, kept = plan[:, 0].tolist(), keep.tolist()
+    ranges = []
+    p0 = 0
+    while p0 < N:
+        p1, nk = p0 + 1, int(kept[p0])
+        while (p1 < N and nk + kept[p1] <= batch
+               and (tops[p1] == tops[p0] or tops[p1] + tile - tops[p0] <= band_rows)):
+            nk += kept[p1]
+            p1 += 1
+        ranges.append((p0, p1))
+        p0 = p1
+    return ranges
+
+
+def _translate_skipping(image, sampler, plan, tile, overlap, batch, return_float, min_tissue, keep, white, black,
+                        mask_channels):
+    """``translate_region`` with ``min_tissue`` or ``keep``: per range of ``plan_region_batches``, the skipped tiles'
+    window weights go to a second ring, the kept tiles are gathered compacted (padded to ``batch``), sampled and blended,
+    and the rows above the next range's first top are finalised against the source (``s2s_region_finalize_mixed``)."""
+    if min_tissue is not None and keep is not None:
+        raise ValueError("translate_region: keep and min_tissue exclude each other")
+    white, black = _check_thresholds(white, black)
+    if min_tissue is not None:
+        min_tissue = float(min_tissue)
+        if not 0.0 <= min_tissue <= 1.0:
+            raise ValueError(f"translate_region: min_tissue must lie in [0, 1], got {min_tissue}")
+    if mask_channels is None:
+        mask_channels = getattr(sampler, "mask_channels", 0)
+    Cm = operator.index(mask_channels)
+    if not 0 <= Cm <= 5:
+        raise ValueError(f"translate_region: mask_channels must lie in 0..5, got {Cm}")
+    C = 3 + Cm
+    H, W = int(image.shape[0]), int(image.shape[1])
+    N = plan.shape[0]
+    on_gpu = image.is_cuda
+    dev = image.device if on_gpu else torch.device("cuda", torch.cuda.current_device())
+    band_rows = band_rows_for(H, W, tile, overlap, batch)
+    if not on_gpu:
+        stage_in = torch.empty((band_rows, W, 3), dtype=torch.uint8, pin_memory=True)
+        band_in = torch.empty((band_rows, W, 3), dtype=torch.uint8, device=dev)
+        in_ready = None                                   # the GPU's last read of stage_in
+    if min_tissue is not None:
+        counts = _count_tissue(image, plan, plan.to(dev), tile, white, black, dev,
+                               *(() if on_gpu else (stage_in, band_in)))
+        counts = counts.tolist()                          # the one host synchronisation skipping adds
+        if min(counts) < 0:
+            raise RuntimeError("translate_region: a tile was counted outside its band")
+        keep = torch.tensor([c >= min_tissue * a for c, a in zip(counts, _tile_areas(plan, H, W, tile).tolist())],
+                            dtype=torch.bool)
+    elif isinstance(keep, torch.Tensor):
+        keep = keep.cpu()
+    ranges = plan_region_batches(plan, keep, batch, band_rows, tile)
+    kept = keep.tolist()
+    # one upload: per range its kept origins, padded to `batch` by repeating the last one, then its skipped origins
+    rows, layout = [], []
+    for p0, p1 in ranges:
+        ks = [p for p in range(p0, p1) if kept[p]]
+        ss = [p for p in range(p0, p1) if not kept[p]]
+        ko = len(rows)
+        if ks:
+            rows += ks + [ks[-1]] * (batch - len(ks))
+        layout.append((len(ks), len(ss), ko, len(rows)))
+        rows += ss
+    origins = plan[rows].contiguous().to(dev)
+    tops = plan[:, 0].tolist()
+    n_kept = sum(kept)
+    x = torch.empty((batch, 3, tile, tile), dtype=torch.float32, device=dev) if n_kept else None
+    acc = torch.zeros((band_rows, W, C + 1), dtype=torch.float32, device=dev)
+    ws = torch.zeros((band_rows, W), dtype=torch.float32, device=dev)
+    want_f = return_float or Cm > 0
+    if on_gpu:
+        res_u8 = out_u8 = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+        res_f = out_f = torch.empty((H, W, C), dtype=torch.float32, device=dev) if want_f else None
+    else:
+        res_u8 = torch.empty((H, W, 3), dtype=torch.uint8)
+        res_f = torch.empty((H, W, C), dtype=torch.float32) if want_f else None
+        out_u8 = torch.empty((band_rows, W, 3), dtype=torch.uint8, device=dev)
+        out_f = torch.empty((band_rows, W, C), dtype=torch.float32, device=dev) if want_f else None
+        stage_u8 = torch.empty((band_rows, W, 3), dtype=torch.uint8, pin_memory=True)
+        stage_f = torch.empty((band_rows, W, C), dtype=torch.float32, pin_memory=True) if want_f else None
+    fin = 0                                               # rows [0, fin) are final; fin is the range's first top
+    calls = 0
+    pending = None                                        # host output rows in flight: (event, r0, r1)
+
+    def drain():                                          # host image: staged output rows -> the result
+        ev, a, b = pending
+        ev.synchronize()
+        res_u8[a:b] = stage_u8[:b - a]
+        if res_f is not None:
+            res_f[a:b] = stage_f[:b - a]
+
+    for (p0, p1), (nk, ns, ko, so) in zip(ranges, layout):
+        r0, r1 = tops[p0], min(H, tops[p1 - 1] + tile)
+        done = tops[p1] if p1 < N else H                  # no later tile covers rows above the next range's first top
+        if on_gpu:
+            src, src_top = image, 0
+        else:
+            rs = r1 if nk else done                       # without kept tiles only the rows to finalise are read
+            if rs > r0:
+                if in_ready is not None:
+                    in_ready.synchronize()                # the previous upload has left stage_in
+                stage_in[:rs - r0].copy_(image[r0:rs])
+                band_in[:rs - r0].copy_(stage_in[:rs - r0], non_blocking=True)
+                in_ready = torch.cuda.Event()
+                in_ready.record()
+            src, src_top = band_in[:max(rs - r0, 1)], r0
+        if ns:
+            ops.region_skip_weight(origins[so:so + ns], tile, overlap, ws, H, r0, r1)
+        if nk:
+            ops.region_gather(src, src_top, H, W, origins[ko:ko + batch], tile, x)
+            out = sampler(x)
+            calls += 1
+            probs = None
+            if isinstance(out, tuple):
+                if len(out) != 2:
+                    raise ValueError(f"translate_region: a tuple from the sampler must be (image, probabilities), "
+                                     f"got {len(out)} items")
+                out, probs = out
+                probs = _check_output(probs, batch, tile, dev, "probabilities", channels=5)
+            out = _check_output(out, batch, tile, dev, "image")
+            if 3 + (0 if probs is None else probs.shape[1]) != C:
+                raise ValueError(f"translate_region: the sampler changed its output channels: mask_channels says "
+                                 f"{Cm} probability channels, it returned {0 if probs is None else probs.shape[1]}")
+            ops.region_blend(out[:nk], None if probs is None else probs[:nk], origins[ko:ko + nk], overlap, acc,
+                             band_rows, H, W, r0, r1)
+        if done > fin:
+            if on_gpu:
+                ops.region_finalize_mixed(acc, ws, fin, done, src, src_top, out_u8, out_f, 0)
+            else:
+                ops.region_finalize_mixed(acc, ws, fin, done, src, src_top, out_u8, out_f, fin)
+                if pending is not None:
+                    drain()                               # stage_u8 / stage_f are free again
+                n = done - fin
+                stage_u8[:n].copy_(out_u8[:n], non_blocking=True)
+                if out_f is not None:
+                    stage_f[:n].copy_(out_f[:n], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                pending = (ev, fin, done)
+            fin = done
+    if pending is not None:
+        drain()
+    translate_region.last_stats = {"tiles": N, "batches": len(ranges), "band_rows": band_rows,
+                                   "accumulator_bytes": (acc.numel() + ws.numel()) * acc.element_size(),
+                                   "channels": C, "kept": n_kept, "skipped": N - n_kept, "sampler_calls": calls}
+    extra = []
+    if Cm:
+        extra.append(res_f[..., 3:])
+    if return_float:
+        extra.append(res_f[..., :3])
+    return (res_u8, *extra) if extra else res_u8
 
 
 def multitask_sampler(module, num_steps: int, graph: bool = True, *, method: str = "euler", atol: float = 1e-4,
@@ -235,4 +499,5 @@ def multitask_sampler(module, num_steps: int, graph: bool = True, *, method: str
         return solve(flow, _prep_source(x), method, num_steps, atol, rtol, graph=graph,
                      per_sample=method == "dopri5", cache_on=captures), probs.float()
 
+    sample.mask_channels = 1 if module.num_classes is None else int(module.num_classes)   # translate_region's layout
     return sample
