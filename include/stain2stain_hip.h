@@ -396,6 +396,38 @@ int s2s_image_quality_u8(const void* a, long pitch_a, long img_a, const void* b,
 int s2s_image_quality_finalize(const double* part, int B, int C, int H, int W, int win, float range, float* out,
                                void* stream);
 
+/* ---- stain quantification (stain_quant.hip) -------------------------------------
+ * Colour deconvolution (Ruifrok & Johnston 2001) and the positive-area burden.  od(u) = od_table[u], a HOST array of 256
+ * floats (-log10(max(u, 1) / 255), computed in double by the caller); `unmix` is a HOST array of 12 floats: m[3 ch + k],
+ * the inverse of the stain basis, then the three thresholds.  c_k = ((od_r m_rk) + (od_g m_gk)) + (od_b m_bk), every
+ * operation rounded in fp32; a pixel is tissue by the rule of s2s_region_tissue_count (white, black) and positive for
+ * stain k iff tissue and c_k > thr_k.  An owner is a cell_h x cell_w cell of one sample (cell = image: one owner per
+ * sample); owner index (n * Gy + gy) * Gx + gx.  A cell is cut into chunks of 16 rows x 1024 columns,
+ * s2s_stain_quant_chunks(cell_h, cell_w) of them; a workgroup reduces one chunk and writes 7 (single) or 5 (paired)
+ * 8-byte partials at part[(owner * chunks + chunk) * K]: no atomics, bit-reproducible, independent of the banding.
+ * s2s_stain_quant_u8: uint8 [B][.][W][3], row pitches and sample strides in bytes; paired != 0 reads b too.  The buffers
+ *   hold image rows [band_top, band_top + band_h) of an H x W image; chunk rows [g0, g0 + ng) are computed, chunk row
+ *   g = gy * cdiv(cell_h, 16) + cy reading image rows from gy * cell_h + 16 cy on.
+ * s2s_stain_quant_f32: float [B][3][H][W] in the network's range through the save conversion
+ *   trunc(clamp((x * 0.5 + 0.5) * 255, 0, 255)); one owner per sample.
+ * s2s_stain_quant_finalize: single: counts long [owners][4] = tissue, positive_k; sums double [owners][3] = sum over
+ *   tissue of max(c_k, 0); out float [owners][6] = burden_k = positive_k / max(tissue, 1), mean_od_k.  paired (for
+ *   `stain`): counts long [owners][5] = tissue_a, tissue_b, positive in both, in a only, in b only; out float
+ *   [owners][5] = burden_a, burden_b, |burden_a - burden_b|, Dice, IoU (1 when both masks are empty); sums unused.
+ * s2s_stain_separate: uint8 [B][H][W][3] (pitch, img_stride in bytes) or float [B][3][H][W] (elements) -> out float
+ *   [B][3][H][W], the concentrations. */
+int s2s_stain_quant_chunks(int cell_h, int cell_w);
+int s2s_stain_quant_u8(const void* a, long pitch_a, long img_a, const void* b, long pitch_b, long img_b, int paired,
+                       int B, int band_top, int band_h, int H, int W, int cell_h, int cell_w, int g0, int ng,
+                       const float* od_table, const float* unmix, int white, int black, int stain, double* part,
+                       void* stream);
+int s2s_stain_quant_f32(const float* a, const float* b, int paired, int B, int H, int W, const float* od_table,
+                        const float* unmix, int white, int black, int stain, double* part, void* stream);
+int s2s_stain_quant_finalize(const double* part, long owners, int nchunk, int paired, long* counts, double* sums,
+                             float* out, void* stream);
+int s2s_stain_separate(const void* img, int is_f32, long pitch, long img_stride, int B, int H, int W,
+                       const float* od_table, const float* unmix, float* out, void* stream);
+
 /* ---- loss variants and class conditioning (loss_variants.hip) -- SURVEY section 8 row f4 -----------------
  * ROI-weighted MSE (conditional_flow_matching_masked.py:76-90): w = 1 + roi_lambda * mask,
  *   out[0] = sum(w (v-u)^2) / (sum(w) + 1e-8), w broadcast over C.  v, u: float[B][C][HW]; mask: float[B][HW];

@@ -75,6 +75,13 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// The tissue rule of the region kernels (region.hip, stain_quant.hip): integer and exact.  white in 1..256, black in
+// 0..255; 0 disables the dark test.
+__device__ __forceinline__ int is_tissue(unsigned r, unsigned g, unsigned b, int white, int black) {
+  const int mn = (int)min(r, min(g, b)), mx = (int)max(r, max(g, b));
+  return (mn < white && mx >= black) ? 1 : 0;
+}
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // Opt a kernel into more than 64 KiB of dynamic LDS.  The attribute is a property of the (kernel, device) pair, so a

@@ -184,11 +184,6 @@ __global__ void region_finalize_kernel(float* __restrict__ acc, int band_rows, i
 
 // ---- tissue-aware regions: background tiles are measured, skipped and passed through --------
 
-__device__ __forceinline__ int is_tissue(unsigned r, unsigned g, unsigned b, int white, int black) {
-  const int mn = (int)min(r, min(g, b)), mx = (int)max(r, max(g, b));
-  return (mn < white && mx >= black) ? 1 : 0;
-}
-
 // One workgroup of 256 lanes per tile; counts[k] = tissue pixels of the tile's intersection with the image (reflected
 // padding is not counted).  Lanes walk the in-image rows as the gather does: one lane per 4 consecutive pixels, three
 // dword loads when the 12 bytes are aligned and the quad is whole, bytes otherwise.  Integer count per lane, xor-shuffle

@@ -100,20 +100,24 @@ class GenerationEval:
 
 def generation_values(state: GenerationEval, key, encoder, flow_decoder, time_dim: int, x0: torch.Tensor,
                       x1: torch.Tensor, num_steps: int, method: str, graph: bool, quantize: bool,
-                      accumulator: Optional["EvalAccumulator"]) -> Dict[str, torch.Tensor]:
+                      accumulator: Optional["EvalAccumulator"], stain: Optional[dict] = None) -> Dict[str, torch.Tensor]:
     """``x0`` carried to t = 1 by ``samplers.solve`` on the eval-mode network, scored against ``x1``
     (``image_metrics.image_quality``): the per-sample {"psnr", "ssim", "mae", "mse"}.  ``method="dopri5"`` runs the
     per-sample controller (``per_sample=True``, as ``region.multitask_sampler`` does), so that a sample's score does not
-    depend on its batch mates, at the default tolerances; ``num_steps`` plays no role then.  The caller sets the
-    workspace owner and the grad mode."""
-    from . import image_metrics, samplers
+    depend on its batch mates, at the default tolerances; ``num_steps`` plays no role then.  ``stain`` (a dict of
+    ``stain_quant.stain_agreement``'s arguments) adds "stain/burden_abs_err", "stain/dice" and "stain/iou".  The caller
+    sets the workspace owner and the grad mode."""
+    from . import image_metrics, samplers, stain_quant
     if method not in samplers.SOLVER_METHODS:
         raise ValueError(f"method must be one of {', '.join(map(repr, samplers.SOLVER_METHODS))}, got {method!r}")
     f, holder = state.velocity(key, encoder, flow_decoder, time_dim)
     x = samplers._prep_source(x0)
     pred = samplers.solve(f, x, method, num_steps, graph=graph, per_sample=method == "dopri5",
                           cache_on=holder if graph else None)
-    values = image_metrics.image_quality(pred, x1.detach().float().contiguous(), quantize=quantize)
+    target = x1.detach().float().contiguous()
+    values = image_metrics.image_quality(pred, target, quantize=quantize)
+    if stain is not None:
+        values.update(stain_quant.agreement_values(pred, target, stain))
     if accumulator is not None:
         accumulator.add({k: v.mean() for k, v in values.items()}, int(x.shape[0]))
     return values

@@ -247,16 +247,21 @@ region_quality.last_stats: Optional[Dict[str, int]] = None
 
 
 def generation_quality(sampler: Callable, source: torch.Tensor, target: torch.Tensor, accumulator=None,
-                       **metric_args) -> Dict[str, torch.Tensor]:
+                       stain: Optional[dict] = None, **metric_args) -> Dict[str, torch.Tensor]:
     """``image_quality(sampler(source), target, **metric_args)``: the per-sample dict of one generated batch.  A sampler
     that returns a tuple (image, ...) is scored on its image.  ``accumulator`` (an ``EvalAccumulator``): the batch means
-    of the four keys are added to it with weight B, so its epoch mean is the mean over every image."""
+    of the keys are added to it with weight B, so its epoch mean is the mean over every image.  ``stain``: a dict of
+    ``stain_quant.stain_agreement``'s keyword arguments (``{}`` for its defaults) adds ``"stain/burden_abs_err"``,
+    ``"stain/dice"`` and ``"stain/iou"``; ``None`` (the default) changes nothing."""
     pred = sampler(source)
     if isinstance(pred, tuple):
         pred = pred[0]
     if not isinstance(pred, torch.Tensor):
         raise TypeError(f"generation_quality: the sampler must return a tensor, got {type(pred).__name__}")
     values = image_quality(pred, target, **metric_args)
+    if stain is not None:
+        from . import stain_quant
+        values.update(stain_quant.agreement_values(pred, target, stain))
     if accumulator is not None:
         accumulator.add({k: v.mean() for k, v in values.items()}, int(pred.shape[0]))
     return values

@@ -250,14 +250,15 @@ class MultiTaskTrainer:
     def evaluate_generation(self, source: torch.Tensor, target: torch.Tensor, num_steps: int = 50,
                             method: str = "euler", graph: bool = False, use_ema: bool = False,
                             accumulator: Optional[evaluation.EvalAccumulator] = None,
-                            quantize: bool = True) -> Dict[str, torch.Tensor]:
+                            quantize: bool = True, stain: Optional[dict] = None) -> Dict[str, torch.Tensor]:
         """Image quality of the flow head's generated batch against the paired ``target``: per-sample {"psnr", "ssim",
         "mae", "mse"} (fp32 [B] device tensors), as ``CFMTrainer.evaluate_generation``.  The reference's ``generate``
-        also returns the mask; it plays no role here.  ``method="dopri5"``: the per-sample controller, as there.  Touches no training state and uses ``evaluate``'s workspaces."""
+        also returns the mask; it plays no role here.  ``method="dopri5"``: the per-sample controller, as there.  Touches no training state and uses ``evaluate``'s workspaces.
+        ``stain``: the stain-agreement keys, as there."""
         enc, fdec, _ = self.ema_model() if use_ema else (self.encoder, self.flow_decoder, self.seg_decoder)
         with ops.workspace_owner(self._eval_owner), evaluation.eval_grad_mode():
             return evaluation.generation_values(self._generation, bool(use_ema), enc, fdec, self.time_emb_dim, source,
-                                                target, num_steps, method, graph, quantize, accumulator)
+                                                target, num_steps, method, graph, quantize, accumulator, stain)
 
     def close(self) -> None:
         """Release evaluate()'s workspaces and evaluate_generation()'s captured sampler steps."""

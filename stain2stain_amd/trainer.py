@@ -341,7 +341,7 @@ class CFMTrainer:
     def evaluate_generation(self, x0: torch.Tensor, x1: torch.Tensor, num_steps: int = 50, method: str = "euler",
                             graph: bool = False, use_ema: bool = False,
                             accumulator: Optional[evaluation.EvalAccumulator] = None,
-                            quantize: bool = True) -> Dict[str, torch.Tensor]:
+                            quantize: bool = True, stain: Optional[dict] = None) -> Dict[str, torch.Tensor]:
         """Image quality of one generated batch: ``x0`` is carried to t = 1 by ``samplers.solve`` (``method`` one of
         ``samplers.SOLVER_METHODS``, ``num_steps`` for the fixed-step ones; ``graph``: a captured step, kept until the
         next optimiser step) on the eval-mode network and scored against the paired ``x1``.  Returns the per-sample
@@ -351,12 +351,14 @@ class CFMTrainer:
         (eagerly; a capture does) and uses workspaces of its own.  ``accumulator``: the batch means are added with weight
         ``x0.shape[0]``.  ``use_ema``: sample from the averaged network.  ``method="dopri5"`` runs the per-sample
         controller at the default tolerances (a sample's score then does not depend on its batch mates; ``generate``'s
-        default is the batch-wide one) and ignores ``num_steps``."""
+        default is the batch-wide one) and ignores ``num_steps``.  ``stain``: a dict of ``stain_quant.stain_agreement``'s
+        keyword arguments adds "stain/burden_abs_err", "stain/dice" and "stain/iou" (how well the generated stain agrees
+        with the real one on what is positive); ``None``: nothing changes."""
         net = self.ema_model() if use_ema else self.net
         with ops.workspace_owner(self._eval_owner), evaluation.eval_grad_mode():
             return evaluation.generation_values(self._generation, bool(use_ema), net.encoder, net.flow_decoder,
                                                 net.time_embedding.dim, x0, x1, num_steps, method, graph, quantize,
-                                                accumulator)
+                                                accumulator, stain)
 
     def close(self) -> None:
         """Drop the captured graph, its static buffers and the pinned Adam-scalar ring while torch and the HIP runtime are
