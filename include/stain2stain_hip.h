@@ -122,6 +122,24 @@ int s2s_head_loss_fused(int dtype, const void* x, int ldx, const float* w, const
                         float* v_nchw, void* dx, int lddx, float grad_scale, float* part, double* lpart, float* dw,
                         float* dbias, float* loss, int accumulate, int B, int H, int W, int C, int Cout, void* stream);
 
+/* fused tail of the training step: the last BatchNorm + ReLU, the head, the MSE loss, the head's backward and that
+ * BatchNorm's backward in three passes that read the saved conv output `raw` (T, NHWC); neither the last activation nor
+ * its gradient is stored, and the results are those of s2s_bn_relu_apply -> s2s_head_loss_fused -> s2s_bn_relu_bwd.  C = 8 * 2^k <= 512, Cout <= 4.  scale / shift / mean / invstd: s2s_bn_finalize's outputs.
+ * s2s_tail_fwd_loss: g = dv (NCHW fp32 out), v optional, loss, head dW / db, dgamma / dbeta (conv_dbias, optional, is
+ *   set to its exact value 0 unless accumulating) and the per-channel means of the BatchNorm backward in bnwork.
+ *   part: float[blocks][Cout][C+1]; lpart: double[blocks], blocks = s2s_tail_blocks;
+ *   bnwork: float[2*C*nb + 2*C], nb = s2s_bn_bwd_blocks(B, H, W, C)
+ * s2s_tail_bwd_apply: dx = d raw (T, NHWC) from raw, g and bnwork. */
+int s2s_tail_blocks(int B, int H, int W);
+int s2s_tail_fwd_loss(int dtype, const void* raw, int ldx, const float* scale, const float* shift, const float* mean,
+                      const float* invstd, const float* w, const float* bias, const float* u_nchw, float* v_nchw,
+                      float* g_nchw, float grad_scale, float* part, double* lpart, float* bnwork, float* dw,
+                      float* dbias, float* loss, float* dgamma, float* dbeta, float* conv_dbias, int accumulate, int B,
+                      int H, int W, int C, int Cout, void* stream);
+int s2s_tail_bwd_apply(int dtype, const void* raw, int ldx, const float* g_nchw, const float* w, const float* scale,
+                       const float* shift, const float* mean, const float* invstd, const float* gamma,
+                       const float* bnwork, void* dx, int lddx, int B, int H, int W, int C, int Cout, void* stream);
+
 /* ---- BatchNorm2d + ReLU (+ MaxPool2d(2)) (norm_act.hip) -------------------------------------------
  * nn.BatchNorm2d(eps 1e-5, momentum 0.1) -> nn.ReLU of DoubleConv (shared_encoder.py:16-20) and the
  * nn.MaxPool2d(2) of the following Down block (shared_encoder.py:33). */

@@ -677,6 +677,230 @@ bool launch_head_lanes(const void* x, int ldx, const float* w, const float* bias
 #undef S2S_HLN
 }
 
+// ---------------------------------------------------------------------------------------------
+// fused tail of the training step: last BatchNorm + ReLU -> head -> MSE loss -> head backward -> BatchNorm backward.
+// The last activation has one reader (the head) and its gradient one reader (the BatchNorm backward), and the whole
+// chain is local to a pixel, so neither tensor is stored: three passes that read the saved conv output (and write
+// 12.6 + 134 MB) instead of four passes over three 64-channel tensors.
+//   pass A (tail_fwd_loss_kernel): a = relu(scale raw + shift) rounded to T, v = W a + b, g = coef (v - u), partial
+//     sums of the loss and of dW | db; writes only g (and v when asked), both NCHW fp32.
+//   sums (norm_act.hip, bn_relu_bwd_reduce_tail_kernel): da = W^T g rounded to T, sum dz and sum dz xhat, dz = da (a > 0),
+//     then bn_bwd_finalize.
+//   pass B (tail_bwd_apply_kernel): recomputes da from g and writes d raw = gamma invstd (dz - c1 - xhat c2).
+// Every value is rounded where the stored tensors of the unfused chain (bn_relu_apply -> head_loss_lanes_kernel ->
+// bn_relu_bwd_*_flat_kernel) rounded it, with their expressions, and every sum is taken in that chain's order: pass A
+// has head_loss_lanes_kernel's grid and pixel-to-lane map, the sums pass bn_relu_bwd_reduce_flat_kernel's (the two
+// differ, which is why the BatchNorm sums are not taken in pass A).  The results are the chain's, bit for bit.
+// Same lane-per-piece layout as head_loss_lanes_kernel (C = 8 PCB).
+// ---------------------------------------------------------------------------------------------
+// Sum over the PCB lanes that share a pixel, every lane getting the total: the butterfly of head_loss_lanes_kernel
+// (t += t[lane ^ m], m = 1, 2, 4, ...) with DPP moves in place of LDS permutes for m <= 8.  After the two quad steps
+// the four lanes of a quad agree, so the mirrored lane of the other quad (or half row) holds what lane ^ 4 (lane ^ 8)
+// holds: the same additions, bit for bit.  Needs every lane of the wave active.
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+template <int PCB>
+__device__ __forceinline__ float group_sum(float t) {
+  if (PCB >= 2) t += dpp_f32<0xB1>(t);        // quad_perm [1,0,3,2]
+  if (PCB >= 4) t += dpp_f32<0x4E>(t);        // quad_perm [2,3,0,1]
+  if (PCB >= 8) t += dpp_f32<0x141>(t);       // row_half_mirror
+  if (PCB >= 16) t += dpp_f32<0x140>(t);      // row_mirror
+#pragma unroll
+  for (int m = 16; m < PCB; m <<= 1) t += __shfl_xor(t, m, 64);
+  return t;
+}
+
+// a pixel piece as loaded (bf16 stays packed while the load is in flight: 4 VGPRs a stage instead of 8)
+__device__ __forceinline__ bf16x8 tail_ld(const bf16_t* p) { return *reinterpret_cast<const bf16x8*>(p); }
+__device__ __forceinline__ f32x8 tail_ld(const float* p) { return load8(p); }
+__device__ __forceinline__ float tail_at(const bf16x8& v, int k) { return (float)v[k]; }
+__device__ __forceinline__ float tail_at(const f32x8& v, int k) { return v.v[k]; }
+
+template <typename T, int PCB, int MO>
+__global__ __launch_bounds__(256) void tail_fwd_loss_kernel(const T* __restrict__ raw, int ldx,
+                                                            const float* __restrict__ scale, const float* __restrict__ shift,
+                                                            const float* __restrict__ w, const float* __restrict__ bias,
+                                                            const float* __restrict__ u, float* __restrict__ v_out,
+                                                            float* __restrict__ g_out, float coef,
+                                                            float* __restrict__ part, double* __restrict__ lpart,
+                                                            long npix, int HW, int Cout) {
+  constexpr int C = PCB * 8, PPB = 256 / PCB;     // MO: outputs the loops cover (3 for the flow head: 16 fewer VGPRs)
+  __shared__ float fold[256][MO * 8 + 1];
+  __shared__ float dbf[PPB][MO];
+  __shared__ double lred[256];
+  const int tid = threadIdx.x, pc = tid & (PCB - 1), slot = tid / PCB;
+  float wr[MO][8], bo[MO];
+#pragma unroll
+  for (int o = 0; o < MO; ++o) {
+    bo[o] = (o < Cout && bias) ? bias[o] : 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) wr[o][k] = o < Cout ? w[o * C + pc * 8 + k] : 0.f;
+  }
+  float sc[8], sh[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { sc[k] = scale[pc * 8 + k]; sh[k] = shift[pc * 8 + k]; }
+  float dwacc[MO][8], dbacc[MO];
+#pragma unroll
+  for (int o = 0; o < MO; ++o) {
+    dbacc[o] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) dwacc[o][k] = 0.f;
+  }
+  double lsum = 0.0;
+  const int np = (int)npix, stride = (int)gridDim.x * PPB;     // 32-bit pixel indices (checked on the host)
+  // Two pixels ahead: the piece and the targets of the next two iterations are in flight while this one is processed
+  // (with one, 3 waves x 1 KB a SIMD left the pass latency-bound at 1.2 TB/s).  Every lane of a pixel reads its targets
+  // (one address per pixel and output) and forms g itself: no owner-lane broadcast through LDS.
+  struct Stage {
+    decltype(tail_ld((const T*)nullptr)) r;
+    float u[MO];
+    long i;                                                       // offset of output 0 of the pixel in the NCHW tensors
+  };
+  auto fetch = [&](Stage& st, int pf) {       // past the end: the last pixel again (finite values; its g is forced to 0 below)
+    pf = pf < np ? pf : np - 1;
+    st.r = tail_ld(raw + (long)pf * ldx + pc * 8);
+    const int n = pf / HW, q = pf - n * HW;
+    st.i = (long)n * Cout * HW + q;
+#pragma unroll
+    for (int o = 0; o < MO; ++o) st.u[o] = u[st.i + (long)(o < Cout ? o : Cout - 1) * HW];   // (no branch around a load)
+  };
+  Stage sa, sb;
+  fetch(sa, (int)blockIdx.x * PPB + slot);
+  fetch(sb, (int)blockIdx.x * PPB + slot + stride);
+  // one pixel: take the stage's values, refill it two pixels ahead (the two stages alternate, so no register of a load
+  // in flight is copied), then the arithmetic
+  auto step = [&](Stage& st, int p0) {
+    const int p = p0 + slot;
+    const bool ok = p < np;
+    f32x8 r;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r.v[k] = tail_at(st.r, k);
+    float cu[MO];
+#pragma unroll
+    for (int o = 0; o < MO; ++o) cu[o] = st.u[o];
+    const long i0 = st.i;
+    fetch(st, p + 2 * stride);
+    float a[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k)                                   // bn_relu_apply's expression, stored as T
+      a[k] = to_f32(from_f32<T>(fmaxf(fmaf(r.v[k], sc[k], sh[k]), 0.f)));
+    float vv[MO];
+#pragma unroll
+    for (int o = 0; o < MO; ++o) {
+      float t = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) t = fmaf(a[k], wr[o][k], t);
+      vv[o] = group_sum<PCB>(t) + bo[o];
+    }
+    float g[MO];                                                  // (a pixel past the end has g = 0: it adds nothing to any sum)
+#pragma unroll
+    for (int o = 0; o < MO; ++o) {
+      const float d = vv[o] - cu[o];
+      g[o] = (ok && o < Cout) ? coef * d : 0.f;
+      if (ok && o < Cout && (o & (PCB - 1)) == pc) {        // this lane writes output channel o of the pixel
+        const long idx = i0 + (long)o * HW;
+        if (v_out) v_out[idx] = vv[o];
+        lsum += (double)(d * d);
+        g_out[idx] = g[o];
+      }
+    }
+#pragma unroll
+    for (int o = 0; o < MO; ++o) {
+      if (pc == 0) dbacc[o] += g[o];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) dwacc[o][k] = fmaf(g[o], a[k], dwacc[o][k]);
+    }
+  };
+  for (int p0 = (int)blockIdx.x * PPB; p0 < np; p0 += 2 * stride) {
+    step(sa, p0);
+    if (p0 + stride < np) step(sb, p0 + stride);                  // (workgroup-uniform)
+  }
+#pragma unroll
+  for (int o = 0; o < MO; ++o) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) fold[tid][o * 8 + k] = dwacc[o][k];
+    if (pc == 0) dbf[slot][o] = dbacc[o];
+  }
+  lred[tid] = lsum;
+  __syncthreads();
+  const int nout = Cout * (C + 1);
+  for (int id = tid; id < nout; id += 256) {
+    const int o = id / (C + 1), c = id - o * (C + 1);
+    float t = 0.f;
+    if (c < C) {
+      const int cp = c >> 3, k = c & 7;
+      for (int sl = 0; sl < PPB; ++sl) t += fold[sl * PCB + cp][o * 8 + k];
+    } else {
+      for (int sl = 0; sl < PPB; ++sl) t += dbf[sl][o];
+    }
+    part[(long)blockIdx.x * nout + id] = t;
+  }
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) lred[tid] += lred[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) lpart[blockIdx.x] = lred[0];
+}
+
+template <typename T, int PCB, int MO>
+__global__ __launch_bounds__(256) void tail_bwd_apply_kernel(const T* __restrict__ raw, int ldx,
+                                                             const float* __restrict__ g_nchw, const float* __restrict__ w,
+                                                             const float* __restrict__ scale, const float* __restrict__ shift,
+                                                             const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                             const float* __restrict__ gamma, const float* __restrict__ c1,
+                                                             const float* __restrict__ c2, T* __restrict__ dx, int lddx,
+                                                             long npix, int HW, int Cout) {
+  constexpr int C = PCB * 8, PPB = 256 / PCB;     // MO: outputs the loops cover (3 for the flow head: 16 fewer VGPRs)
+  const int tid = threadIdx.x, pc = tid & (PCB - 1), slot = tid / PCB;
+  float wr[MO][8];
+#pragma unroll
+  for (int o = 0; o < MO; ++o)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) wr[o][k] = o < Cout ? w[o * C + pc * 8 + k] : 0.f;
+  float ga[8], k1[8], k2[8], mu[8], is[8], sc[8], sh[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int c = pc * 8 + k;
+    mu[k] = mean[c]; is[k] = invstd[c]; sc[k] = scale[c]; sh[k] = shift[c];
+    ga[k] = gamma[c] * is[k]; k1[k] = c1[c]; k2[k] = c2[c];
+  }
+  // back to front, like the flat apply pass: pass A read the tensor front to back, so its tail is what the memory-side
+  // cache still holds.  The next pixel's piece and gradient are fetched before this one is processed.
+  const int np = (int)npix, stride = (int)gridDim.x * PPB;
+  const int first = (int)blockIdx.x * PPB + slot;
+  const int nit = first < np ? (np - first + stride - 1) / stride : 0;
+  f32x8 r_next;
+  float g_next[MO];
+  auto fetch = [&](int p) {
+    r_next = load8(raw + (long)p * ldx + pc * 8);
+    const int n = p / HW, q = p - n * HW;
+#pragma unroll
+    for (int o = 0; o < MO; ++o) g_next[o] = o < Cout ? g_nchw[((long)n * Cout + o) * HW + q] : 0.f;
+  };
+  if (nit > 0) fetch(first + (nit - 1) * stride);
+  for (int it = nit - 1; it >= 0; --it) {
+    const int p = first + it * stride;
+    const f32x8 r = r_next;
+    float g[MO];
+#pragma unroll
+    for (int o = 0; o < MO; ++o) g[o] = g_next[o];
+    if (it > 0) fetch(p - stride);
+    f32x8 out;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      float t = 0.f;
+#pragma unroll
+      for (int o = 0; o < MO; ++o) t = fmaf(g[o], wr[o][k], t);
+      const float da = to_f32(from_f32<T>(t));
+      const float dz = fmaf(r.v[k], sc[k], sh[k]) > 0.f ? da : 0.f;
+      out.v[k] = ga[k] * (dz - k1[k] - ((r.v[k] - mu[k]) * is[k]) * k2[k]);
+    }
+    store8(dx + (long)p * lddx + pc * 8, out);
+  }
+}
+
 __global__ __launch_bounds__(256) void loss_finalize_kernel(const double* part, int n, double inv_count, float* loss) {
   __shared__ double red[256];
   double s = 0.0;
@@ -871,6 +1095,105 @@ extern "C" int s2s_head_loss_fused(int dtype, const void* x, int ldx, const floa
   hipLaunchKernelGGL(head_wgrad_reduce_kernel, dim3(cdiv(Cout * (C + 1), 8)), dim3(256), 0, s, part, nb, Cout, C,
                      dw, dbias, accumulate);
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, s, lpart, nb, 1.0 / count, loss);
+  S2S_LAUNCH_CHECK();
+  return S2S_OK;
+}
+
+// the BatchNorm backward sums of the tail (reduction pass from g + per-channel finalize) live in norm_act.hip
+int s2s_internal_tail_bn_sums(int dtype, const void* raw, int ldx, const float* g_nchw, const float* w, const float* scale,
+                              const float* shift, const float* mean, const float* invstd, float* work, float* dgamma,
+                              float* dbeta, float* zero_out, int accumulate, int B, int H, int W, int C, int Cout,
+                              hipStream_t s);
+extern "C" int s2s_bn_bwd_blocks(int B, int H, int W, int C);
+
+namespace {
+inline bool tail_shape_ok(int B, int H, int W, int C, int Cout, int ldx) {
+  if (B <= 0 || H <= 0 || W <= 0 || C < 8 || (C % 8) || (ldx % 8) || Cout <= 0 || Cout > HEAD_MAX_COUT) return false;
+  const int pcb = C / 8;
+  if (pcb > 64 || (pcb & (pcb - 1))) return false;
+  return (long)B * H * W < (1L << 31) - (1L << 20);      // 32-bit pixel index (+ one grid stride) in the kernels
+}
+}  // namespace
+
+// workgroups of passes A and B = rows of pass A's partial buffers
+extern "C" int s2s_tail_blocks(int B, int H, int W) { return s2s_head_loss_blocks(B, H, W); }
+
+// Pass A of the fused tail (see tail_fwd_loss_kernel) + the folds of its partial sums (head dW | db, the loss), then the
+// BatchNorm backward's sums from g and their per-channel finalize (dgamma, dbeta, the two means pass B reads; conv_dbias,
+// the gradient of a bias in front of a train-mode BatchNorm, is exactly zero as in s2s_bn_relu_bwd).
+//   part: float[blocks][Cout][C+1]; lpart: double[blocks], blocks = s2s_tail_blocks;
+//   bnwork: float[2*C*nb + 2*C] (sums | c1 | c2), nb = s2s_bn_bwd_blocks; g_nchw: [B][Cout][H][W] fp32 out; v_nchw: optional
+extern "C" int s2s_tail_fwd_loss(int dtype, const void* raw, int ldx, const float* scale, const float* shift,
+                                 const float* mean, const float* invstd, const float* w, const float* bias,
+                                 const float* u_nchw, float* v_nchw, float* g_nchw, float grad_scale, float* part,
+                                 double* lpart, float* bnwork, float* dw, float* dbias, float* loss, float* dgamma,
+                                 float* dbeta, float* conv_dbias, int accumulate, int B, int H, int W, int C, int Cout,
+                                 void* stream) {
+  if (!raw || !scale || !shift || !mean || !invstd || !w || !u_nchw || !g_nchw || !part || !lpart || !bnwork || !dw ||
+      !loss || !dgamma || !dbeta)
+    return S2S_ERR_NULL;
+  if (!tail_shape_ok(B, H, W, C, Cout, ldx)) return S2S_ERR_SHAPE;
+  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  const long npix = (long)B * H * W;
+  const double count = (double)npix * Cout;
+  const int nb = s2s_tail_blocks(B, H, W);
+  hipStream_t s = (hipStream_t)stream;
+  const float coef = (float)(2.0 * (double)grad_scale / count);
+#define S2S_TA(TT, PP)                                                                                               \
+  if (Cout <= 3)                                                                                                     \
+    hipLaunchKernelGGL((tail_fwd_loss_kernel<TT, PP, 3>), dim3(nb), dim3(256), 0, s, (const TT*)raw, ldx, scale,     \
+                       shift, w, bias, u_nchw, v_nchw, g_nchw, coef, part, lpart, npix, H * W, Cout);                \
+  else                                                                                                               \
+  hipLaunchKernelGGL((tail_fwd_loss_kernel<TT, PP, HEAD_MAX_COUT>), dim3(nb), dim3(256), 0, s, (const TT*)raw, ldx, scale, shift,   \
+                     w, bias, u_nchw, v_nchw, g_nchw, coef, part, lpart, npix, H * W, Cout);
+#define S2S_TA_T(TT)                                                                                    \
+  switch (C / 8) {                                                                                      \
+    case 1: { S2S_TA(TT, 1) } break;  case 2: { S2S_TA(TT, 2) } break;  case 4: { S2S_TA(TT, 4) } break;    \
+    case 8: { S2S_TA(TT, 8) } break;  case 16: { S2S_TA(TT, 16) } break; case 32: { S2S_TA(TT, 32) } break;  \
+    default: { S2S_TA(TT, 64) } break;                                                                  \
+  }
+  if (dtype == S2S_BF16) { S2S_TA_T(bf16_t) } else { S2S_TA_T(float) }
+#undef S2S_TA_T
+#undef S2S_TA
+  hipLaunchKernelGGL(head_wgrad_reduce_kernel, dim3(cdiv(Cout * (C + 1), 8)), dim3(256), 0, s, part, nb, Cout, C,
+                     dw, dbias, accumulate);
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, s, lpart, nb, 1.0 / count, loss);
+  if (int rc = s2s_internal_tail_bn_sums(dtype, raw, ldx, g_nchw, w, scale, shift, mean, invstd, bnwork, dgamma, dbeta,
+                                         (conv_dbias && !accumulate) ? conv_dbias : nullptr, accumulate, B, H, W, C,
+                                         Cout, s))
+    return rc;
+  S2S_LAUNCH_CHECK();
+  return S2S_OK;
+}
+
+// Pass B of the fused tail: d raw from the saved conv output, g and the means s2s_tail_fwd_loss left in bnwork.
+extern "C" int s2s_tail_bwd_apply(int dtype, const void* raw, int ldx, const float* g_nchw, const float* w,
+                                  const float* scale, const float* shift, const float* mean, const float* invstd,
+                                  const float* gamma, const float* bnwork, void* dx, int lddx, int B, int H, int W,
+                                  int C, int Cout, void* stream) {
+  if (!raw || !g_nchw || !w || !scale || !shift || !mean || !invstd || !gamma || !bnwork || !dx) return S2S_ERR_NULL;
+  if (!tail_shape_ok(B, H, W, C, Cout, ldx) || (lddx % 8) || lddx < C) return S2S_ERR_SHAPE;
+  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  const long npix = (long)B * H * W;
+  const int nb = s2s_tail_blocks(B, H, W);
+  const float* const c1 = bnwork + (long)2 * C * s2s_bn_bwd_blocks(B, H, W, C);
+  hipStream_t s = (hipStream_t)stream;
+#define S2S_TB(TT, PP)                                                                                              \
+  if (Cout <= 3)                                                                                                    \
+    hipLaunchKernelGGL((tail_bwd_apply_kernel<TT, PP, 3>), dim3(nb), dim3(256), 0, s, (const TT*)raw, ldx, g_nchw,  \
+                       w, scale, shift, mean, invstd, gamma, c1, c1 + C, (TT*)dx, lddx, npix, H * W, Cout);         \
+  else                                                                                                              \
+  hipLaunchKernelGGL((tail_bwd_apply_kernel<TT, PP, HEAD_MAX_COUT>), dim3(nb), dim3(256), 0, s, (const TT*)raw, ldx, g_nchw, w,    \
+                     scale, shift, mean, invstd, gamma, c1, c1 + C, (TT*)dx, lddx, npix, H * W, Cout);
+#define S2S_TB_T(TT)                                                                                    \
+  switch (C / 8) {                                                                                      \
+    case 1: { S2S_TB(TT, 1) } break;  case 2: { S2S_TB(TT, 2) } break;  case 4: { S2S_TB(TT, 4) } break;    \
+    case 8: { S2S_TB(TT, 8) } break;  case 16: { S2S_TB(TT, 16) } break; case 32: { S2S_TB(TT, 32) } break;  \
+    default: { S2S_TB(TT, 64) } break;                                                                  \
+  }
+  if (dtype == S2S_BF16) { S2S_TB_T(bf16_t) } else { S2S_TB_T(float) }
+#undef S2S_TB_T
+#undef S2S_TB
   S2S_LAUNCH_CHECK();
   return S2S_OK;
 }

@@ -494,6 +494,64 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_flat_kernel(const T* _
   }
 }
 
+// The reduction pass of the fused tail (conv_edge.hip): bn_relu_bwd_reduce_flat_kernel with the incoming gradient
+// rebuilt per pixel from g (NCHW fp32, Cout <= 4 planes) the way head_loss_lanes_kernel stored it, da = W^T g rounded
+// to T.  Same grid, same pixel-to-thread map, same expressions: the partial sums are that kernel's, bit for bit.
+template <typename T>
+__global__ __launch_bounds__(256) void bn_relu_bwd_reduce_tail_kernel(const float* __restrict__ g_nchw, const float* __restrict__ w, int Cout, int HW,
+                                               const float* __restrict__ scale, const float* __restrict__ shift,
+                                               const T* __restrict__ x, int ldx, const float* mean, const float* invstd,
+                                               float* part, long npix, int C) {
+  const int PCB = pcb_of(C), WL = 256 / PCB;
+  const int pc = threadIdx.x & (PCB - 1), wl = threadIdx.x / PCB;
+  const int c8 = (blockIdx.x * PCB + pc) * 8;
+  using Acc = typename std::conditional<std::is_same<T, float>::value, double, float>::type;
+  Acc s1[8], s2[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { s1[k] = 0; s2[k] = 0; }
+  if (c8 < C) {
+    float mu[8], is[8], sc[8], sh[8], wr[4][8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { mu[k] = mean[c8 + k]; is[k] = invstd[c8 + k]; sc[k] = scale[c8 + k]; sh[k] = shift[c8 + k]; }
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+#pragma unroll
+      for (int k = 0; k < 8; ++k) wr[o][k] = o < Cout ? w[o * C + c8 + k] : 0.f;
+    for (long p = (long)blockIdx.y * WL + wl; p < npix; p += (long)gridDim.y * WL) {
+      const int pi = (int)p, n = pi / HW, q = pi - n * HW;      // (npix < 2^31, checked on the host)
+      float gv[4];
+#pragma unroll
+      for (int o = 0; o < 4; ++o) {
+        const float t = g_nchw[((long)n * Cout + (o < Cout ? o : Cout - 1)) * HW + q];
+        gv[o] = o < Cout ? t : 0.f;
+      }
+      const f32x8 b = load8(x + p * ldx + c8);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        float t = 0.f;
+#pragma unroll
+        for (int o = 0; o < 4; ++o) t = fmaf(gv[o], wr[o][k], t);
+        const float gk = to_f32(from_f32<T>(t));
+        const float dz = fmaf(b.v[k], sc[k], sh[k]) > 0.f ? gk : 0.f;   // ReLU mask from the conv output
+        s1[k] += (Acc)dz;
+        s2[k] += (Acc)(dz * ((b.v[k] - mu[k]) * is[k]));
+      }
+    }
+  }
+  __shared__ Acc red[2][2304];
+  const int rowlen = PCB * 8 + 1;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { red[0][wl * rowlen + pc * 8 + k] = s1[k]; red[1][wl * rowlen + pc * 8 + k] = s2[k]; }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * PCB * 8; i += 256) {
+    const int which = i / (PCB * 8), cl = i - which * (PCB * 8);
+    Acc s = 0;
+    for (int r = 0; r < WL; ++r) s += red[which][r * rowlen + cl];
+    const int c = blockIdx.x * PCB * 8 + cl;
+    if (c < C) part[((long)which * C + c) * gridDim.y + blockIdx.y] = (float)s;
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void bn_relu_bwd_apply_flat_kernel(const T* __restrict__ g1, int ldg1, const float* __restrict__ scale, const float* __restrict__ shift,
                                               const T* __restrict__ x, int ldx, const float* mean, const float* invstd,
@@ -743,6 +801,33 @@ extern "C" int s2s_bn_relu_bwd_phase(int dtype, const void* g1, int ldg1, const 
     hipLaunchKernelGGL(colsum_finalize_kernel, dim3(cdiv(C, 32)), dim3(1024), 0, s, part2, prereduce(part2, nb, C, s),
                        C, dbias_conv, accumulate);
   S2S_LAUNCH_CHECK();
+  return S2S_OK;
+}
+
+// The BatchNorm backward sums of the fused tail (conv_edge.hip): the reduction pass from g and the per-channel finalize,
+// as phase 1 of s2s_bn_relu_bwd_phase runs them.  work: float[2*C*blocks + 2*C] (sums | c1 | c2), blocks =
+// s2s_bn_bwd_blocks(B, H, W, C).
+int s2s_internal_tail_bn_sums(int dtype, const void* raw, int ldx, const float* g_nchw, const float* w, const float* scale,
+                              const float* shift, const float* mean, const float* invstd, float* work, float* dgamma,
+                              float* dbeta, float* zero_out, int accumulate, int B, int H, int W, int C, int Cout,
+                              hipStream_t s) {
+  const int nb = red_blocks(B, H, W, C);
+  float* const c1 = work + (long)2 * C * nb;
+  const long npix = (long)B * H * W;
+  dim3 grid(cdiv(C / 8, host_pcb(C)), nb);
+  if (dtype == S2S_BF16)
+    hipLaunchKernelGGL(bn_relu_bwd_reduce_tail_kernel<bf16_t>, grid, dim3(256), 0, s, g_nchw, w, Cout, H * W, scale, shift,
+                       (const bf16_t*)raw, ldx, mean, invstd, work, npix, C);
+  else if (dtype == S2S_F32)
+    hipLaunchKernelGGL(bn_relu_bwd_reduce_tail_kernel<float>, grid, dim3(256), 0, s, g_nchw, w, Cout, H * W, scale, shift,
+                       (const float*)raw, ldx, mean, invstd, work, npix, C);
+  else return S2S_ERR_DTYPE;
+  if (finalize_tpc(nb) == 256)
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel<256>, dim3(C), dim3(256), 0, s, work, nb, C, (double)npix, dgamma, dbeta,
+                       accumulate, c1, c1 + C, zero_out);
+  else
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel<64>, dim3(cdiv(C, 4)), dim3(256), 0, s, work, nb, C, (double)npix, dgamma,
+                       dbeta, accumulate, c1, c1 + C, zero_out);
   return S2S_OK;
 }
 

@@ -237,7 +237,7 @@ class LayerCtx:
     x0: Optional[torch.Tensor]          # conv input (NHWC), or the NCHW image for the stem
     x1: Optional[torch.Tensor]
     raw: torch.Tensor                   # conv output
-    act: torch.Tensor                   # ReLU output
+    act: Optional[torch.Tensor]         # ReLU output (None: the fused tail never stores it)
     stats: torch.Tensor                 # [4, C]: mean, invstd, scale, shift
     count: Optional[int] = None         # elements per channel the statistics were taken over (None = the local B*H*W)
     sync: Optional["SyncBNExchange"] = None     # SyncBatchNorm: the exchange the forward used (its backward uses it too)
@@ -263,6 +263,7 @@ class DecCtx:
     skips: List[torch.Tensor] = field(default_factory=list)
     layers: List[Tuple[LayerCtx, LayerCtx]] = field(default_factory=list)
     v: torch.Tensor = None
+    tail: Optional[Tuple[torch.Tensor, torch.Tensor]] = None    # fused tail: (g, work) of ops.tail_fwd_loss
 
 
 def _stem_as_conv(x_nchw: torch.Tensor, dtype: torch.dtype) -> bool:
@@ -278,42 +279,49 @@ def _stem_image(x_nchw: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     return ops.p2p_pack_input(x_nchw, None, torch.empty((B, H, W, 8), dtype=dtype, device=x_nchw.device))
 
 
-def _conv_bn_relu(cb: ConvBN, x0, x1, dtype, training: bool, want_pool: bool = False, stem: bool = False):
-    """Returns (LayerCtx or None, act, pooled)."""
+def _conv_bn_stats(cb: ConvBN, x0, x1, dtype, stem: bool = False):
+    """Training mode: the convolution and its finalized batch statistics.  Returns (raw, stats, count, exchange)."""
     bn = cb.bn
     bias = cb.conv.bias.detach() if cb.conv.bias is not None else None
+    # A conv bias in front of a train-mode BatchNorm cancels in the normalised output (and its gradient is exactly
+    # zero): the bf16 MFMA kernel is launched WITHOUT it -- its persistent form has no bias path -- and the bias only
+    # enters the running mean (ops.bn_finalize, conv_bias).  The saved conv output and the saved mean are both those
+    # of the unbiased convolution, so the backward is unchanged.  (fp32 parity mode and the stem add it as before.)
+    late_bias = None
+    if stem and _stem_as_conv(x0, dtype):
+        raw, stat = ops.conv3x3(_stem_image(x0, dtype), None, cb.packed(dtype)[0], None, cb.cout, want_stats=True)
+        late_bias = bias
+    elif stem:
+        raw, stat = ops.stem_fwd(x0, cb.conv.weight.detach(), bias, dtype, want_stats=True)
+    elif dtype == torch.bfloat16 and bias is not None:
+        raw, stat = ops.conv3x3(x0, x1, cb.packed(dtype)[0], None, cb.cout, want_stats=True)
+        late_bias = bias
+    else:
+        raw, stat = ops.conv3x3(x0, x1, cb.packed(dtype)[0], bias, cb.cout, want_stats=True)
+    count = raw.shape[0] * raw.shape[1] * raw.shape[2]
+    sx = sync_bn if sync_bn is not None else _module_exchange(bn)
+    if sx is not None:      # statistics over the global batch: all-reduce the per-channel sums, finalize on those
+        sums = ops.bn_partial_sums(stat)
+        sx(sums)
+        stat = sums.view(2, -1, 1)
+        count *= sx.world
+    if count <= 1:      # torch.nn.functional.batch_norm raises the same way in training mode
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size "
+                         f"{[raw.shape[0], raw.shape[3], raw.shape[1], raw.shape[2]]}")
+    track = bn.track_running_stats and bn.running_mean is not None
+    mutation_epoch[0] += 1
+    st = ops.bn_finalize(stat, count, bn.weight.detach(), bn.bias.detach(),
+                         bn.running_mean if track else None, bn.running_var if track else None,
+                         bn.num_batches_tracked if track else None,
+                         BN_MOMENTUM if bn.momentum is None else bn.momentum, bn.eps, conv_bias=late_bias)
+    return raw, st, count, sx
+
+
+def _conv_bn_relu(cb: ConvBN, x0, x1, dtype, training: bool, want_pool: bool = False, stem: bool = False):
+    """Returns (LayerCtx or None, act, pooled)."""
+    bias = cb.conv.bias.detach() if cb.conv.bias is not None else None
     if training:
-        # A conv bias in front of a train-mode BatchNorm cancels in the normalised output (and its gradient is exactly
-        # zero): the bf16 MFMA kernel is launched WITHOUT it -- its persistent form has no bias path -- and the bias only
-        # enters the running mean (ops.bn_finalize, conv_bias).  The saved conv output and the saved mean are both those
-        # of the unbiased convolution, so the backward is unchanged.  (fp32 parity mode and the stem add it as before.)
-        late_bias = None
-        if stem and _stem_as_conv(x0, dtype):
-            raw, stat = ops.conv3x3(_stem_image(x0, dtype), None, cb.packed(dtype)[0], None, cb.cout, want_stats=True)
-            late_bias = bias
-        elif stem:
-            raw, stat = ops.stem_fwd(x0, cb.conv.weight.detach(), bias, dtype, want_stats=True)
-        elif dtype == torch.bfloat16 and bias is not None:
-            raw, stat = ops.conv3x3(x0, x1, cb.packed(dtype)[0], None, cb.cout, want_stats=True)
-            late_bias = bias
-        else:
-            raw, stat = ops.conv3x3(x0, x1, cb.packed(dtype)[0], bias, cb.cout, want_stats=True)
-        count = raw.shape[0] * raw.shape[1] * raw.shape[2]
-        sx = sync_bn if sync_bn is not None else _module_exchange(bn)
-        if sx is not None:      # statistics over the global batch: all-reduce the per-channel sums, finalize on those
-            sums = ops.bn_partial_sums(stat)
-            sx(sums)
-            stat = sums.view(2, -1, 1)
-            count *= sx.world
-        if count <= 1:      # torch.nn.functional.batch_norm raises the same way in training mode
-            raise ValueError(f"Expected more than 1 value per channel when training, got input size "
-                             f"{[raw.shape[0], raw.shape[3], raw.shape[1], raw.shape[2]]}")
-        track = bn.track_running_stats and bn.running_mean is not None
-        mutation_epoch[0] += 1
-        st = ops.bn_finalize(stat, count, bn.weight.detach(), bn.bias.detach(),
-                             bn.running_mean if track else None, bn.running_var if track else None,
-                             bn.num_batches_tracked if track else None,
-                             BN_MOMENTUM if bn.momentum is None else bn.momentum, bn.eps, conv_bias=late_bias)
+        raw, st, count, sx = _conv_bn_stats(cb, x0, x1, dtype, stem)
         act, pooled = ops.bn_relu_apply(raw, st[2], st[3], want_pool=want_pool)
         return LayerCtx(x0, x1, raw, act, st, count if sx is not None else None, sx), act, pooled
     ss = cb.eval_affine()
@@ -421,6 +429,50 @@ def _conv_bn_relu_bwd(cb: ConvBN, lc: LayerCtx, g1, gp, grads, accumulate: bool,
 
 
 # ------------------------------------------------------------------------------------------------
+# fused tail: last BatchNorm + ReLU, head, MSE loss and their backward straight from the last conv output
+# ------------------------------------------------------------------------------------------------
+def _conv_bn_tail(cb: ConvBN, x0, dtype):
+    """The decoder's last conv + BatchNorm (training mode) stopped after the statistics: the activation is not stored,
+    ``decoder_tail_loss`` and ``decoder_backward`` work from ``raw`` and ``stats``.  Returns (LayerCtx, act or None); with
+    SyncBatchNorm (the sums of the backward are exchanged between the passes: not wired) the layer is the ordinary one."""
+    raw, st, count, sx = _conv_bn_stats(cb, x0, None, dtype)
+    if sx is not None:
+        act, _ = ops.bn_relu_apply(raw, st[2], st[3])
+        return LayerCtx(x0, None, raw, act, st, count, sx), act
+    return LayerCtx(x0, None, raw, None, st), None
+
+
+def decoder_tail_loss(dec, ctx: DecCtx, u_nchw: torch.Tensor, grads: Dict[str, torch.Tensor], want_v: bool = False,
+                      accumulate: bool = False):
+    """Pass A and the BatchNorm sums of the fused tail on a context of ``decoder_forward(..., with_head=False, fuse_tail=True)``: the loss
+    mean((v - u)^2), the head's gradients and the last BatchNorm's dgamma / dbeta into ``grads``.  Returns (loss, v or
+    None); ``decoder_backward`` picks ``ctx.tail`` up."""
+    cb = dec.up_blocks[-1][1]
+    lc = ctx.layers[-1][1]
+    p = cb.prefix
+    i_conv, i_bn = cb.idx
+    loss, g, v, work = ops.tail_fwd_loss(
+        lc.raw, lc.stats, dec.outc.weight.detach(), dec.outc.bias.detach() if dec.outc.bias is not None else None,
+        u_nchw, _g(grads, "outc.weight"), _g(grads, "outc.bias") if dec.outc.bias is not None else None,
+        _g(grads, f"{p}.{i_bn}.weight"), _g(grads, f"{p}.{i_bn}.bias"),
+        _g(grads, f"{p}.{i_conv}.bias") if cb.conv.bias is not None else None, want_v=want_v, accumulate=accumulate)
+    ctx.tail = (g, work)
+    ctx.v = v
+    return loss, v
+
+
+def _conv_bn_tail_bwd(dec, cb: ConvBN, lc: LayerCtx, tail, grads, accumulate: bool):
+    """Backward of the tail layer's conv: pass B writes ``d raw``, the weight and data gradients follow as in
+    ``_conv_bn_relu_bwd`` (its BatchNorm gradients came out of pass A)."""
+    g, work = tail
+    draw = ops.tail_bwd_apply(lc.raw, lc.stats, dec.outc.weight.detach(), g, cb.bn.weight.detach(), work)
+    dw = _g(grads, f"{cb.prefix}.{cb.idx[0]}.weight")
+    run_on_side(lambda: ops.conv3x3_wgrad(draw, lc.x0, lc.x1, dw, accumulate), (draw,))
+    dx, _ = ops.conv3x3(draw, None, cb.packed(draw.dtype)[1], None, cb.cin)
+    return dx
+
+
+# ------------------------------------------------------------------------------------------------
 # encoder
 # ------------------------------------------------------------------------------------------------
 def encoder_forward(blocks: Sequence[Tuple[ConvBN, ConvBN]], x_nchw: torch.Tensor, dtype: torch.dtype,
@@ -466,9 +518,14 @@ def encoder_backward(blocks: Sequence[Tuple[ConvBN, ConvBN]], ctx: EncCtx, dfeat
 # decoder
 # ------------------------------------------------------------------------------------------------
 def decoder_forward(dec, bottleneck: torch.Tensor, skips: Sequence[torch.Tensor], t_emb: torch.Tensor,
-                    dtype: torch.dtype, training: bool, with_head: bool = True) -> DecCtx:
+                    dtype: torch.dtype, training: bool, with_head: bool = True, fuse_tail: bool = False) -> DecCtx:
     """dec: FlowMatchingDecoder container (time_mlp, time_proj, up_blocks, outc).  with_head=False stops at the
-    last activation (ctx.lows[-1]); the fused head+loss kernel of the training step takes it from there."""
+    last activation (ctx.lows[-1]); the fused head+loss kernel of the training step takes it from there.
+    ``fuse_tail`` (training mode, with_head=False, channel counts ``ops.tail_fusable`` takes, no SyncBatchNorm): stop
+    one step earlier, after the last layer's statistics -- its LayerCtx has ``act = None``, ctx.lows[-1] is None and
+    ``decoder_tail_loss`` takes it from there.  Anything else keeps the ordinary chain."""
+    fuse_tail = (fuse_tail and training and not with_head and len(dec.up_blocks) > 0
+                 and ops.tail_fusable(dec.up_blocks[-1][1].cout, dec.outc.weight.shape[0]))
     ctx = DecCtx(dtype, t_emb)
     repack_stale([cb for pair in dec.up_blocks for cb in pair], dtype)
     tbias = None
@@ -484,7 +541,10 @@ def decoder_forward(dec, bottleneck: torch.Tensor, skips: Sequence[torch.Tensor]
         up = torch.empty((B, Hs, Ws, x.shape[3]), dtype=dtype, device=x.device)
         ops.upsample2x_fwd(x, up, tbias if i == 0 else None)
         lc1, a1, _ = _conv_bn_relu(c1, skip, up, dtype, training)
-        lc2, a2, _ = _conv_bn_relu(c2, a1, None, dtype, training)
+        if fuse_tail and i == len(dec.up_blocks) - 1:
+            lc2, a2 = _conv_bn_tail(c2, a1, dtype)
+        else:
+            lc2, a2, _ = _conv_bn_relu(c2, a1, None, dtype, training)
         ctx.lows.append(x); ctx.ups.append(up); ctx.skips.append(skip); ctx.layers.append((lc1, lc2))
         x = a2
     ctx.lows.append(x)  # head input
@@ -500,7 +560,9 @@ def decoder_backward(dec, ctx: DecCtx, dv: Optional[torch.Tensor], grads: Dict[s
     """Returns (dbottleneck, [dskip per level], dt_emb or None); all NHWC in the compute dtype.
     ``on_group_done()``: after the head, after every conv + BatchNorm layer (last Up block first, its second conv before
     its first), then after the time path (only when the decoder has one)."""
-    if g_head is not None:      # head gradients already produced by the fused head+loss kernel
+    if ctx.tail is not None:    # fused tail: the head's gradients came out of decoder_tail_loss, g stays 3 channels wide
+        g = None
+    elif g_head is not None:    # head gradients already produced by the fused head+loss kernel
         g = g_head
     else:
         g = ops.head_bwd(dv, ctx.lows[-1], dec.outc.weight.detach(), _g(grads, "outc.weight"),
@@ -512,7 +574,10 @@ def decoder_backward(dec, ctx: DecCtx, dv: Optional[torch.Tensor], grads: Dict[s
     for i in range(len(ctx.layers) - 1, -1, -1):
         c1, c2 = dec.up_blocks[i]
         lc1, lc2 = ctx.layers[i]
-        ga1 = _conv_bn_relu_bwd(c2, lc2, g, None, grads, accumulate, need_dx=True)
+        if ctx.tail is not None and i == nup - 1:
+            ga1 = _conv_bn_tail_bwd(dec, c2, lc2, ctx.tail, grads, accumulate)
+        else:
+            ga1 = _conv_bn_relu_bwd(c2, lc2, g, None, grads, accumulate, need_dx=True)
         if on_group_done is not None:
             on_group_done()
         dcat = _conv_bn_relu_bwd(c1, lc1, ga1, None, grads, accumulate, need_dx=True)

@@ -103,6 +103,7 @@ class MultiTaskTrainer:
                                            + list(seg_decoder.up_blocks), self._dtype)
         self._side = ops.side_stream_for(dev)
         self.overlap_wgrad = True
+        self.fuse_tail = True           # the flow decoder's tail without its last activation, as CFMTrainer.fuse_tail
         self._group = 0
         self._eval_owner = object()         # evaluate()'s workspaces, released by close()
         self._generation = evaluation.GenerationEval()      # evaluate_generation()'s velocities and captured steps
@@ -138,15 +139,20 @@ class MultiTaskTrainer:
         ectx1 = engine.encoder_forward(enc._blocks, xt, dt, True)
         temb = ops.time_embedding(t, self.time_emb_dim)
         f1 = ectx1.feats
-        dctx_f = engine.decoder_forward(fdec, f1[-1], f1[:-1][::-1], temb, dt, True, with_head=False)
+        dctx_f = engine.decoder_forward(fdec, f1[-1], f1[:-1][::-1], temb, dt, True, with_head=False,
+                                        fuse_tail=self.fuse_tail and not want_outputs)
         ectx2 = engine.encoder_forward(enc._blocks, x0, dt, True)
         f2 = ectx2.feats
         dctx_s = engine.decoder_forward(sdec, f2[-1], f2[:-1][::-1], None, dt, True)
         logits = dctx_s.v
-        flow, g_head, v = ops.head_loss_fused(dctx_f.lows[-1], fdec.outc.weight.detach(),
-                                              fdec.outc.bias.detach() if fdec.outc.bias is not None else None, ut,
-                                              self.grads_flow["outc.weight"], self.grads_flow.get("outc.bias"),
-                                              want_v=want_outputs)
+        if dctx_f.lows[-1] is None:     # fused tail (engine.decoder_tail_loss)
+            g_head = None
+            flow, v = engine.decoder_tail_loss(fdec, dctx_f, ut, self.grads_flow, want_v=want_outputs)
+        else:
+            flow, g_head, v = ops.head_loss_fused(dctx_f.lows[-1], fdec.outc.weight.detach(),
+                                                  fdec.outc.bias.detach() if fdec.outc.bias is not None else None, ut,
+                                                  self.grads_flow["outc.weight"], self.grads_flow.get("outc.bias"),
+                                                  want_v=want_outputs)
         w = float(self.seg_loss_weight)
         if self.num_classes is not None:
             tgt = mask[:, 0] if (mask.dim() == 4 and mask.shape[1] == 1) else mask

@@ -457,6 +457,61 @@ def head_loss_fused(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tenso
     return loss, dx, v
 
 
+def tail_fusable(C: int, cout: int) -> bool:
+    """Channel counts the fused tail (tail_fwd_loss / tail_bwd_apply) takes: C = 8 * 2^k <= 512, cout <= 4."""
+    pcb = C // 8
+    return C % 8 == 0 and 1 <= pcb <= 64 and pcb & (pcb - 1) == 0 and 1 <= cout <= 4
+
+
+@_timed("tail_fwd_loss")
+def tail_fwd_loss(raw: torch.Tensor, stats: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
+                  u_nchw: torch.Tensor, dw: torch.Tensor, dbias: Optional[torch.Tensor], dgamma: torch.Tensor,
+                  dbeta: torch.Tensor, dbias_conv: Optional[torch.Tensor], want_v: bool = False,
+                  grad_scale: float = 1.0, accumulate: bool = False):
+    """Pass A and the BatchNorm sums of the fused tail: from the last layer's conv output ``raw`` and its ``stats``
+    (bn_finalize's rows), what bn_relu_apply -> head_loss_fused -> the reduction half of bn_relu_bwd compute, bit for
+    bit, without storing the activation or its gradient.  Returns (loss, g, v or None, work): ``g`` = dv [B, cout, H, W] fp32, ``work`` the BatchNorm
+    backward's per-channel means for ``tail_bwd_apply``.  Writes the head's dW / db and the layer's dgamma / dbeta (and
+    the exact zero of its conv-bias gradient)."""
+    B, H, W, C = raw.shape
+    cout = w.shape[0]
+    if not tail_fusable(C, cout):
+        raise RuntimeError(f"stain2stain_amd: the fused tail does not take C = {C}, cout = {cout}")
+    px, ldx = _nhwc(raw)
+    dev = raw.device
+    g = torch.empty((B, cout, H, W), dtype=torch.float32, device=dev)
+    v = torch.empty((B, cout, H, W), dtype=torch.float32, device=dev) if want_v else None
+    nb = _L().s2s_tail_blocks(B, H, W)
+    part = torch.empty((nb, cout, C + 1), dtype=torch.float32, device=dev)
+    lpart = torch.empty((nb,), dtype=torch.float64, device=dev)
+    work = torch.empty((2 * C * _L().s2s_bn_bwd_blocks(B, H, W, C) + 2 * C,), dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    rc = _L().s2s_tail_fwd_loss(_dt(raw), px, ldx, stats[2].data_ptr(), stats[3].data_ptr(), stats[0].data_ptr(),
+                                stats[1].data_ptr(), _f32(w.reshape(cout, C)), _f32(bias), _f32(u_nchw), _f32(v),
+                                _f32(g), float(grad_scale), _f32(part), lpart.data_ptr(), _f32(work),
+                                _f32(dw.reshape(cout, C)), _f32(dbias), loss.data_ptr(), _f32(dgamma), _f32(dbeta),
+                                _f32(dbias_conv), int(accumulate), B, H, W, C, cout, _stream())
+    _native.check(rc, "tail_fwd_loss")
+    return loss, g, v, work
+
+
+@_timed("tail_bwd_apply")
+def tail_bwd_apply(raw: torch.Tensor, stats: torch.Tensor, w: torch.Tensor, g: torch.Tensor, gamma: torch.Tensor,
+                   work: torch.Tensor) -> torch.Tensor:
+    """Pass B of the fused tail: the gradient wrt ``raw`` (what bn_relu_bwd returns) from ``raw``, ``g`` and ``work``."""
+    B, H, W, C = raw.shape
+    cout = w.shape[0]
+    px, ldx = _nhwc(raw)
+    if tuple(g.shape) != (B, cout, H, W) or work.numel() != 2 * C * _L().s2s_bn_bwd_blocks(B, H, W, C) + 2 * C:
+        raise RuntimeError("stain2stain_amd: tail_bwd_apply operands do not belong to this tail_fwd_loss")
+    dx = torch.empty((B, H, W, C), dtype=raw.dtype, device=raw.device)
+    rc = _L().s2s_tail_bwd_apply(_dt(raw), px, ldx, _f32(g), _f32(w.reshape(cout, C)), stats[2].data_ptr(),
+                                 stats[3].data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), _f32(gamma),
+                                 _f32(work), dx.data_ptr(), C, B, H, W, C, cout, _stream())
+    _native.check(rc, "tail_bwd_apply")
+    return dx
+
+
 # ------------------------------------------------------------------------------------------------
 # BatchNorm + ReLU (+ pool)
 # ------------------------------------------------------------------------------------------------

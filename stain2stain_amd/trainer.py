@@ -132,6 +132,12 @@ class CFMTrainer:
         # S2S_WGRAD_STREAM=0 keeps everything on one stream
         self._side = ops.side_stream_for(dev)
         self.overlap_wgrad = True       # bench.py clears it on the steps whose kernels it brackets with HIP events
+        # the last BatchNorm + ReLU, the head, the loss and their backward straight from the last conv output
+        # (engine.decoder_tail_loss): neither the last activation nor its gradient is stored, the results are the
+        # chain's bit for bit.  False keeps the chain
+        # bn_relu_apply -> head_loss_fused -> bn_relu_bwd, as does a forward_backward that is asked for the velocity
+        # (want_v: the inspecting call, which leaves every layer's activation in its context)
+        self.fuse_tail = True
         self.graph = graph
         self._graph_step = CapturedStep()
         self._ema = None
@@ -177,13 +183,18 @@ class CFMTrainer:
             ectx = engine.encoder_forward(enc._blocks, xt, dt, True)
             temb = ops.time_embedding(t, net.time_embedding.dim)
             feats = ectx.feats
-            dctx = engine.decoder_forward(dec, feats[-1], feats[:-1][::-1], temb, dt, True, with_head=False)
-        # head conv + loss + their backward in one sweep over the last activation
-        loss, g_head, v = ops.head_loss_fused(dctx.lows[-1], dec.outc.weight.detach(),
-                                              dec.outc.bias.detach() if dec.outc.bias is not None else None, ut,
-                                              self.grads_dec["outc.weight"], self.grads_dec.get("outc.bias"),
-                                              want_v=want_v)
-        dctx.v = v
+            dctx = engine.decoder_forward(dec, feats[-1], feats[:-1][::-1], temb, dt, True, with_head=False,
+                                          fuse_tail=self.fuse_tail and not want_v)
+        if dctx.lows[-1] is None:       # fused tail: the loss and the head's gradients straight from the last conv output
+            g_head = None
+            loss, v = engine.decoder_tail_loss(dec, dctx, ut, self.grads_dec, want_v=want_v)
+        else:
+            # head conv + loss + their backward in one sweep over the last activation
+            loss, g_head, v = ops.head_loss_fused(dctx.lows[-1], dec.outc.weight.detach(),
+                                                  dec.outc.bias.detach() if dec.outc.bias is not None else None, ut,
+                                                  self.grads_dec["outc.weight"], self.grads_dec.get("outc.bias"),
+                                                  want_v=want_v)
+            dctx.v = v
         self.bucketer.start_step()
         self._group = 0
         # (the scope's exit joins the side stream: whatever reads the gradients next -- Adam, a test -- is on the compute
