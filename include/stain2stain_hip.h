@@ -446,6 +446,39 @@ int s2s_stain_quant_finalize(const double* part, long owners, int nchunk, int pa
 int s2s_stain_separate(const void* img, int is_f32, long pitch, long img_stride, int B, int H, int W,
                        const float* od_table, const float* unmix, float* out, void* stream);
 
+/* ---- Macenko stain normalisation (stain_norm.hip) --------------------------------
+ * The uint8 buffers hold image rows [band_top, band_top + band_h) of B images of H x W RGB pixels; pitch and img_stride
+ * in bytes, any pitch >= 3 W, any base alignment.  od_table as in stain quantification.  A pixel is KEPT iff
+ * black <= max(R, G, B) <= u_beta (u_beta = floor(255 exp(-beta)), Macenko's OD cut-off on bytes).
+ * s2s_stain_moments_u8: q_table is a HOST array of 256 ints, rint(od_table[u] * 2^12).  A workgroup reduces one chunk of
+ *   16 rows x 1024 columns and writes ten int64 partials (n, sum q_c, sum q_c q_d for rr rg rb gg gb bb over the kept
+ *   pixels) at part[((n * cdiv(H, 16) + cy) * cdiv(W, 1024) + cx) * 10]; s2s_stain_moments_slots(B, H, W) chunks in
+ *   all.  band_top must be a multiple of 16, band_h too unless the band ends the image, and band_h <= 16 * 65535.
+ * s2s_stain_moments_finalize: the ten int64 sums over nslots chunks.
+ * s2s_stain_angle_hist_u8: plane is a HOST array of 6 floats, plane[2 ch + k], the two leading eigenvectors.  Per kept
+ *   pixel x = ((od_r v1_r) + (od_g v1_g)) + (od_b v1_b), y likewise with v2, d = |x| + |y| (d == 0: skipped),
+ *   s = y / d, bin = clamp(floor((s + 1) * 2048), 0, 4095), every operation rounded in fp32; hist long [4096].
+ * s2s_stain_conc_hist_u8: unmix is a HOST array of 9 floats m[3 ch + k]; c_k as in stain quantification for k = 0, 1,
+ *   bin = clamp(floor(c_k * 1024), 0, 4095); hist long [2][4096].
+ *   Both histograms are ADDED to with 64-bit integer atomics (bit-reproducible); reset != 0 zeroes hist first, in a
+ *   launch of its own on the same stream: the first band of a call passes 1.
+ * s2s_stain_normalize_u8: no pixel is gated.  coef is a HOST array of 17 floats: m[3 ch + k] (9), the two concentration
+ *   scales, the reference vectors ref[3 k + ch] (6).  c'_k = c_k * scale_k, od'_ch = (c'_0 ref_0ch) + (c'_1 ref_1ch),
+ *   u'_ch = clamp(rint(255 * exp2(od'_ch * -log2(10))), 0, 255).  out_f32 == 0: uint8 [B][H][W][3] with out_pitch /
+ *   out_img in bytes; else float [B][3][H][W] = (u' / 255 - 0.5) / 0.5 (out_pitch, out_img ignored). */
+long s2s_stain_moments_slots(int B, int H, int W);
+int s2s_stain_moments_u8(const void* img, long pitch, long img_stride, int B, int band_top, int band_h, int H, int W,
+                         const int* q_table, int u_beta, int black, long* part, void* stream);
+int s2s_stain_moments_finalize(const long* part, long nslots, long* out, void* stream);
+int s2s_stain_angle_hist_u8(const void* img, long pitch, long img_stride, int B, int band_top, int band_h, int H, int W,
+                            const float* od_table, const float* plane, int u_beta, int black, int reset, long* hist,
+                            void* stream);
+int s2s_stain_conc_hist_u8(const void* img, long pitch, long img_stride, int B, int band_top, int band_h, int H, int W,
+                           const float* od_table, const float* unmix, int u_beta, int black, int reset, long* hist,
+                           void* stream);
+int s2s_stain_normalize_u8(const void* img, long pitch, long img_stride, int B, int H, int W, const float* od_table,
+                           const float* coef, void* out, long out_pitch, long out_img, int out_f32, void* stream);
+
 /* ---- loss variants and class conditioning (loss_variants.hip) -- SURVEY section 8 row f4 -----------------
  * ROI-weighted MSE (conditional_flow_matching_masked.py:76-90): w = 1 + roi_lambda * mask,
  *   out[0] = sum(w (v-u)^2) / (sum(w) + 1e-8), w broadcast over C.  v, u: float[B][C][HW]; mask: float[B][HW];

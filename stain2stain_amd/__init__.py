@@ -25,6 +25,7 @@ from .region import multitask_sampler, plan_region_batches, plan_tiles, tissue_c
 from .image_metrics import generation_quality, image_quality, plan_bands, region_quality
 from .stain_quant import (region_stain_agreement, region_stain_map, stain_agreement, stain_matrix, stain_quantify,
                           stain_separate)
+from .stain_norm import REFERENCE_HE, StainFit, fit_stains, normalize_region, stain_normalize
 
 __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeEmbedding", "FlowUNet",
            "ConditionalFlowMatcher", "ConditionalFlowMatchingModule", "MultiTaskFlowMatchingModule", "euler_generate", "dopri5_generate", "euler_integrate", "dopri5_integrate", "SolverConfig", "GraphedVelocity",
@@ -35,4 +36,4 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "EvalAccumulator", "plan_tiles", "translate_region", "tissue_counts", "plan_region_batches", "multitask_sampler", "FIXED_STEP_METHODS",
            "fixed_step_generate", "fixed_step_integrate", "image_quality", "region_quality", "generation_quality",
            "plan_bands", "stain_matrix", "stain_quantify", "stain_agreement", "stain_separate", "region_stain_map",
-           "region_stain_agreement"]
+           "region_stain_agreement", "fit_stains", "stain_normalize", "normalize_region", "StainFit", "REFERENCE_HE"]
