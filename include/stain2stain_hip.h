@@ -188,6 +188,12 @@ int s2s_upsample2x_bilinear_ac_fwd(int dtype, const void* x, int ldx, const floa
                                    int Hin, int Win, int Hout, int Wout, int C, void* stream);
 int s2s_upsample2x_bilinear_ac_bwd(int dtype, const void* dy, int lddy, void* dx, int lddx, int B, int Hin, int Win,
                                    int Hout, int Wout, int C, void* stream);
+/* test-facing: the per-pixel window kernel that the production backward replaced; same arguments, same bits */
+int s2s_upsample2x_bilinear_ac_bwd_ref(int dtype, const void* dy, int lddy, void* dx, int lddx, int B, int Hin,
+                                       int Win, int Hout, int Wout, int C, void* stream);
+/* test-facing, no launch: which backward kernel the shape takes (0 branching gather, 1 per-pixel window, 2 the 2 x 2
+ * kernel; < 0 the launch's shape error); reference != 0: as the _ref entry point chooses */
+int s2s_upsample2x_bwd_family(int lddy, int lddx, int B, int Hin, int Win, int Hout, int Wout, int C, int reference);
 int s2s_pixel_sum(int dtype, const void* x, int ldx, float* out_nc, int B, int HW, int C, int accumulate,
                   void* stream);
 

@@ -221,6 +221,171 @@ __global__ void upsample2x_bwd_win_kernel(const T* __restrict__ dy, int lddy, T*
   }
 }
 
+// 8 channels as loaded (bf16: 4 registers, fp32: 8), widened to fp32 only where they are used; the widening is exact
+template <typename T> struct Raw8;
+template <> struct Raw8<bf16_t> { bf16x8 a; };
+template <> struct Raw8<float> { f32x4 a, b; };
+__device__ __forceinline__ Raw8<bf16_t> load_raw8(const bf16_t* p) {
+  Raw8<bf16_t> r;
+  r.a = *reinterpret_cast<const bf16x8*>(p);
+  return r;
+}
+__device__ __forceinline__ Raw8<float> load_raw8(const float* p) {
+  Raw8<float> r;
+  r.a = *reinterpret_cast<const f32x4*>(p);
+  r.b = *reinterpret_cast<const f32x4*>(p + 4);
+  return r;
+}
+__device__ __forceinline__ f32x8 widen8(const Raw8<bf16_t>& r) {
+  f32x8 o;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) o.v[i] = (float)r.a[i];
+  return o;
+}
+__device__ __forceinline__ f32x8 widen8(const Raw8<float>& r) {
+  f32x8 o;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { o.v[i] = r.a[i]; o.v[4 + i] = r.b[i]; }
+  return o;
+}
+
+// an empty statement that makes the compiler hold r's current value in registers here
+__device__ __forceinline__ void pin8(f32x8& r) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(r.v[i]));
+}
+
+// The production backward for maps of 4 .. 4096 source pixels per axis: the same per-output chain as the window kernel
+// above (acc = fmaf(wy * wx, g, acc), rows ascending, columns ascending within a row, weights from ac_weight_of), with
+// the window placed in closed form and shared between neighbours.
+//
+// For n_in in 4..4096 every destination with a non-zero weight on source index i lies in [2i - 1, 2i + 2] (in exact
+// arithmetic the source coordinate dst (n-1)/(2n-1) is an integer only at dst = 0 and 2n - 1, and is at least
+// 1/(2n-1) away from one elsewhere, far more than the fp32 rounding of scale * dst; the two end points carry weight 0
+// or fall on the clamped index; checked exhaustively on the CPU with the kernel's fp32 arithmetic, w1 taken both as a
+// rounded subtract and as a fused multiply-subtract).  So a 4 x 4 window holds every term of the 5 x 5 one that is
+// not multiplied by 0, and a term multiplied by 0 leaves acc unchanged for finite g: the results are the window
+// kernel's bit for bit.  The windows of source pixels 2a and 2a + 1 overlap in two of their four rows / columns, so a
+// thread produces a 2 x 2 block of source pixels of one channel piece from ONE 6 x 6 set of loads: 9 loads of 16 B per
+// output instead of 25.
+//
+// Layout as in the forward: a workgroup owns one pair of source rows (and one group of PCB channel pieces); lanes walk
+// the channel pieces of a pixel first, the remaining 256/PCB thread slots walk the pixel pairs of the row.  Row taps,
+// row weights and row pointers are wave-uniform and there is no per-element div/mod.  Neighbouring row pairs share two
+// of their six dy rows; workgroup ids are dealt so that the ids congruent mod 8 (which share an XCD's L2 under the
+// round-robin dispatch) take a CONTIGUOUS run of row pairs -- a speed choice only, any placement gives the same result.
+template <typename T>
+__global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 2) void upsample2x_bwd_quad_kernel(const T* __restrict__ dy, int lddy,
+                                                                  T* __restrict__ dx, int lddx, int B, int Hin,
+                                                                  int Win, int Hout, int Wout, int padT, int padL,
+                                                                  int C, int nwork) {
+  const int cp = C >> 3;
+  const int Hu = 2 * Hin, Wu = 2 * Win;
+  const float sh = (float)(Hin - 1) / (float)(Hu - 1), sw = (float)(Win - 1) / (float)(Wu - 1);
+  const int PCB = rs_pcb(C), WL = 256 / PCB;
+  const int pc = threadIdx.x & (PCB - 1), slot = threadIdx.x / PCB;
+  const int HP = (Hin + 1) >> 1, WP = (Win + 1) >> 1;
+  // bijective deal of the workgroup ids: class b % 8 takes a contiguous run
+  const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, cls = blockIdx.x & 7;
+  const int wgid = (cls < r ? cls * (q + 1) : r * (q + 1) + (cls - r) * q) + (blockIdx.x >> 3);
+  const int chunk = wgid / nwork, work = wgid - chunk * nwork;       // channel group outermost
+  // an odd map's last pair is moved back by one: it recomputes the pixel before it (same chain, same bits, written
+  // twice), so every thread stores its four pixels unconditionally -- with conditional stores the compiler sank the
+  // accumulation into the branches and kept all 36 loads alive (spills)
+  const int n = work / HP, iy0 = min(2 * (work - n * HP), Hin - 2);
+  const int piece = chunk * PCB + pc;
+  if (piece >= cp) return;
+  const int c8 = piece * 8;
+
+  float wyA[4], wyB[4];                     // rows 2 iy0 - 1 + j: j = 0..3 feed iy0, j = 2..5 feed iy0 + 1
+  const T* rowp[6];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    const int uy = 2 * iy0 - 1 + j;
+    const bool in = uy >= 0 && uy <= Hu - 1;
+    if (j < 4) wyA[j] = in ? ac_weight_of(uy, Hin, sh, iy0) : 0.f;
+    if (j >= 2) wyB[j - 2] = in ? ac_weight_of(uy, Hin, sh, iy0 + 1) : 0.f;
+    int oy = uy + padT;
+    oy = oy < 0 ? 0 : (oy > Hout - 1 ? Hout - 1 : oy);
+    rowp[j] = dy + ((long)n * Hout + oy) * Wout * lddy;      // wave-uniform; the lane's channel offset goes into off[]
+  }
+  T* const dr0 = dx + ((long)n * Hin + iy0) * Win * lddx + c8;
+  T* const dr1 = dr0 + (long)Win * lddx;
+
+#pragma unroll 1
+  for (int px = slot; px < WP; px += WL) {
+    const int ix0 = min(2 * px, Win - 2);
+    float wxA[4], wxB[4];
+    int off[6];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) {
+      const int ux = 2 * ix0 - 1 + m;
+      const bool in = ux >= 0 && ux <= Wu - 1;
+      if (m < 4) wxA[m] = in ? ac_weight_of(ux, Win, sw, ix0) : 0.f;
+      if (m >= 2) wxB[m - 2] = in ? ac_weight_of(ux, Win, sw, ix0 + 1) : 0.f;
+      int ox = ux + padL;
+      ox = ox < 0 ? 0 : (ox > Wout - 1 ? Wout - 1 : ox);
+      off[m] = ox * lddy + c8;
+    }
+    f32x8 a00, a01, a10, a11;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a00.v[k] = a01.v[k] = a10.v[k] = a11.v[k] = 0.f;
+    // one row of raw loads at a time: nothing moves across a row's end, so the register need stays at one row of
+    // loads beside the four accumulators whatever the scheduler would like to hoist (it spilled otherwise); the
+    // other waves of the SIMD cover the latency
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      Raw8<T> cur[6];
+#pragma unroll
+      for (int m = 0; m < 6; ++m) cur[m] = load_raw8(rowp[j] + off[m]);
+      f32x8 g[6];
+#pragma unroll
+      for (int m = 0; m < 6; ++m) g[m] = widen8(cur[m]);
+      if (j < 4) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+          const float w = wyA[j] * wxA[m];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) a00.v[k] = fmaf(w, g[m].v[k], a00.v[k]);
+        }
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+          const float w = wyA[j] * wxB[m];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) a01.v[k] = fmaf(w, g[m + 2].v[k], a01.v[k]);
+        }
+      }
+      if (j >= 2) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+          const float w = wyB[j - 2] * wxA[m];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) a10.v[k] = fmaf(w, g[m].v[k], a10.v[k]);
+        }
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+          const float w = wyB[j - 2] * wxB[m];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) a11.v[k] = fmaf(w, g[m + 2].v[k], a11.v[k]);
+        }
+      }
+      // the accumulators are pinned at the end of the row: without it the compiler sinks the fmas of three of the four
+      // pixels below the last row and keeps all 36 loads alive (spills)
+      if (j < 4) { pin8(a00); pin8(a01); }
+      if (j >= 2) { pin8(a10); pin8(a11); }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // An odd map's moved-back pair stores a row / column that the pair before it stores too, from another thread or
+    // workgroup at the same time.  That is safe only because both write the same bits: the pixel is the second of one
+    // pair and the first of the other, and both run the same chain on it (same rows, same ac_weight_of arguments,
+    // same fmaf order).  Keep the two halves of the accumulation identical.
+    store8(dr0 + ix0 * lddx, a00);
+    store8(dr0 + (ix0 + 1) * lddx, a01);
+    store8(dr1 + ix0 * lddx, a10);
+    store8(dr1 + (ix0 + 1) * lddx, a11);
+  }
+}
+
 // out[n][c] (+)= sum over the H*W pixels of x[n][.][.][c]   (gradient of the broadcast time bias)
 template <typename T>
 __global__ void pixel_sum_kernel(const T* __restrict__ x, int ldx, float* __restrict__ out, int HW, int C,
@@ -229,8 +394,20 @@ __global__ void pixel_sum_kernel(const T* __restrict__ x, int ldx, float* __rest
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   const int rg = threadIdx.x >> 6;  // 4 pixel groups
   float s = 0.f;
-  if (c < C)
-    for (int p = rg; p < HW; p += 4) s += to_f32(x[((long)n * HW + p) * ldx + c]);
+  if (c < C) {
+    // a thread's loads are issued ahead of its adds, sixteen at a time; the adds keep their order (p ascending)
+    constexpr int U = 16;
+    const T* const xp = x + (long)n * HW * ldx + c;
+    int p = rg;
+    for (; p + 4 * (U - 1) < HW; p += 4 * U) {
+      float v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[u] = to_f32(xp[(long)(p + 4 * u) * ldx]);
+#pragma unroll
+      for (int u = 0; u < U; ++u) s += v[u];
+    }
+    for (; p < HW; p += 4) s += to_f32(xp[(long)p * ldx]);
+  }
   __shared__ float red[4][64];
   red[rg][threadIdx.x & 63] = s;
   __syncthreads();
@@ -276,8 +453,24 @@ extern "C" int s2s_upsample2x_bilinear_ac_fwd(int dtype, const void* x, int ldx,
   return S2S_OK;
 }
 
-extern "C" int s2s_upsample2x_bilinear_ac_bwd(int dtype, const void* dy, int lddy, void* dx, int lddx, int B, int Hin,
-                                              int Win, int Hout, int Wout, int C, void* stream) {
+namespace {
+
+// Which backward kernel a launch takes (UpBwdFamily; s2s_upsample2x_bwd_family hands it to tests): the branching gather
+// for maps of fewer than 4 source pixels on an axis, the 2 x 2 kernel where its window placement is proven (4..4096
+// source pixels per axis) and its 32-bit offsets inside a row hold, else the per-pixel window kernel.
+enum UpBwdFamily { kUpBwdGather = 0, kUpBwdWindow = 1, kUpBwdQuad = 2 };
+
+int upsample2x_bwd_family(int lddy, int lddx, int B, int Hin, int Win, int Wout, int C, bool reference) {
+  if (!(Hin > 3 && Win > 3)) return kUpBwdGather;
+  const long nwork = (long)B * ((Hin + 1) / 2);
+  const bool quad = !reference && Hin <= 4096 && Win <= 4096 && (long)Wout * lddy < (1L << 31) &&
+                    (long)Win * lddx < (1L << 31) && nwork * cdiv(C / 8, 32) < (1L << 31);
+  return quad ? kUpBwdQuad : kUpBwdWindow;
+}
+
+// `reference`: the per-pixel 5 x 5 window kernel that the 2 x 2 kernel replaced (tests compare the two bit for bit)
+int upsample2x_bwd_launch(int dtype, const void* dy, int lddy, void* dx, int lddx, int B, int Hin, int Win, int Hout,
+                          int Wout, int C, void* stream, bool reference) {
   if (!dy || !dx) return S2S_ERR_NULL;
   if (B <= 0 || Hin <= 0 || Win <= 0 || C <= 0 || (C % 8) || (lddy % 8) || (lddx % 8)) return S2S_ERR_SHAPE;
   if (Hout < 2 * Hin || Wout < 2 * Win) return S2S_ERR_SHAPE;
@@ -286,9 +479,23 @@ extern "C" int s2s_upsample2x_bilinear_ac_bwd(int dtype, const void* dy, int ldd
   if (total >= (1L << 31) - (1L << 22)) return S2S_ERR_SHAPE;   // 32-bit element index in the kernel
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(ew_grid(total));
-  const bool win = Hin > 3 && Win > 3;       // at most five contributing rows / columns per source pixel (else the branching gather)
   if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
-#define S2S_UPB(KERN, TT)                                                                                            \
+  const int family = upsample2x_bwd_family(lddy, lddx, B, Hin, Win, Wout, C, reference);
+  const bool win = family != kUpBwdGather;   // at most five contributing rows / columns per source pixel
+  const int nchunk = cdiv(C / 8, 32);        // rs_pcb(C) channel pieces per workgroup; one group whenever C <= 256
+  const long nwork = (long)B * ((Hin + 1) / 2);
+  if (family == kUpBwdQuad) {
+    const dim3 qgrid((unsigned)(nwork * nchunk));
+    if (dtype == S2S_BF16)
+      hipLaunchKernelGGL(upsample2x_bwd_quad_kernel<bf16_t>, qgrid, dim3(256), 0, s, (const bf16_t*)dy, lddy,
+                         (bf16_t*)dx, lddx, B, Hin, Win, Hout, Wout, padT, padL, C, (int)nwork);
+    else
+      hipLaunchKernelGGL(upsample2x_bwd_quad_kernel<float>, qgrid, dim3(256), 0, s, (const float*)dy, lddy, (float*)dx,
+                         lddx, B, Hin, Win, Hout, Wout, padT, padL, C, (int)nwork);
+    S2S_LAUNCH_CHECK();
+    return S2S_OK;
+  }
+#define S2S_UPB(KERN, TT)                                                                                           \
   hipLaunchKernelGGL(KERN<TT>, grid, dim3(256), 0, s, (const TT*)dy, lddy, (TT*)dx, lddx, B, Hin, Win, Hout, Wout,   \
                      padT, padL, C)
   if (dtype == S2S_BF16) { if (win) S2S_UPB(upsample2x_bwd_win_kernel, bf16_t); else S2S_UPB(upsample2x_bwd_kernel, bf16_t); }
@@ -296,6 +503,29 @@ extern "C" int s2s_upsample2x_bilinear_ac_bwd(int dtype, const void* dy, int ldd
 #undef S2S_UPB
   S2S_LAUNCH_CHECK();
   return S2S_OK;
+}
+
+}  // namespace
+
+extern "C" int s2s_upsample2x_bilinear_ac_bwd(int dtype, const void* dy, int lddy, void* dx, int lddx, int B, int Hin,
+                                              int Win, int Hout, int Wout, int C, void* stream) {
+  return upsample2x_bwd_launch(dtype, dy, lddy, dx, lddx, B, Hin, Win, Hout, Wout, C, stream, false);
+}
+
+// test-facing: the kernel the production entry point replaced, on the same arguments
+extern "C" int s2s_upsample2x_bilinear_ac_bwd_ref(int dtype, const void* dy, int lddy, void* dx, int lddx, int B,
+                                                  int Hin, int Win, int Hout, int Wout, int C, void* stream) {
+  return upsample2x_bwd_launch(dtype, dy, lddy, dx, lddx, B, Hin, Win, Hout, Wout, C, stream, true);
+}
+
+// test-facing, no launch: 0 = branching gather, 1 = per-pixel window kernel, 2 = 2 x 2 kernel, < 0 = the shape error the
+// launch would return.  reference != 0: as s2s_upsample2x_bilinear_ac_bwd_ref chooses.
+extern "C" int s2s_upsample2x_bwd_family(int lddy, int lddx, int B, int Hin, int Win, int Hout, int Wout, int C,
+                                         int reference) {
+  if (B <= 0 || Hin <= 0 || Win <= 0 || C <= 0 || (C % 8) || (lddy % 8) || (lddx % 8)) return S2S_ERR_SHAPE;
+  if (Hout < 2 * Hin || Wout < 2 * Win) return S2S_ERR_SHAPE;
+  if ((long)B * Hin * Win * (C / 8) >= (1L << 31) - (1L << 22)) return S2S_ERR_SHAPE;
+  return upsample2x_bwd_family(lddy, lddx, B, Hin, Win, Wout, C, reference != 0);
 }
 
 extern "C" int s2s_pixel_sum(int dtype, const void* x, int ldx, float* out_nc, int B, int HW, int C, int accumulate,

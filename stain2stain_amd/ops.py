@@ -629,14 +629,25 @@ def upsample2x_fwd(x: torch.Tensor, out: torch.Tensor, bias_nc: Optional[torch.T
 
 
 @_timed("upsample2x_bwd")
-def upsample2x_bwd(dy: torch.Tensor, hin: int, win: int) -> torch.Tensor:
+def upsample2x_bwd(dy: torch.Tensor, hin: int, win: int, _reference: bool = False) -> torch.Tensor:
+    """``_reference`` (tests only): the per-pixel window kernel that the 2 x 2 kernel replaced; same bits."""
     B, Hout, Wout, C = dy.shape
     pdy, lddy = _nhwc(dy)
     dx = torch.empty((B, hin, win, C), dtype=dy.dtype, device=dy.device)
-    rc = _L().s2s_upsample2x_bilinear_ac_bwd(_dt(dy), pdy, lddy, dx.data_ptr(), C, B, hin, win, Hout, Wout, C,
-                                             _stream())
+    fn = _L().s2s_upsample2x_bilinear_ac_bwd_ref if _reference else _L().s2s_upsample2x_bilinear_ac_bwd
+    rc = fn(_dt(dy), pdy, lddy, dx.data_ptr(), C, B, hin, win, Hout, Wout, C, _stream())
     _native.check(rc, "upsample2x_bwd")
     return dx
+
+
+def upsample2x_bwd_family(dy: torch.Tensor, hin: int, win: int, _reference: bool = False) -> int:
+    """Which kernel ``upsample2x_bwd`` launches for this gradient (tests): 0 branching gather, 1 per-pixel window,
+    2 the 2 x 2 kernel."""
+    B, Hout, Wout, C = dy.shape
+    rc = _L().s2s_upsample2x_bwd_family(dy.stride(2), C, B, hin, win, Hout, Wout, C, int(_reference))
+    if rc < 0:
+        _native.check(rc, "upsample2x_bwd_family")
+    return rc
 
 
 def pixel_sum(x: torch.Tensor) -> torch.Tensor:
