@@ -439,7 +439,11 @@ int s2s_image_quality_finalize(const double* part, int B, int C, int H, int W, i
  *   `stain`): counts long [owners][5] = tissue_a, tissue_b, positive in both, in a only, in b only; out float
  *   [owners][5] = burden_a, burden_b, |burden_a - burden_b|, Dice, IoU (1 when both masks are empty); sums unused.
  * s2s_stain_separate: uint8 [B][H][W][3] (pitch, img_stride in bytes) or float [B][3][H][W] (elements) -> out float
- *   [B][3][H][W], the concentrations. */
+ *   [B][3][H][W], the concentrations.
+ * s2s_stain_mask_u8 / s2s_stain_mask_f32: the positive mask of stain `stain` as bytes, bit 0 = positive, bit 1 = tissue,
+ *   written into mask [B][H][.] (mask_pitch, mask_stride in bytes) at the image's own rows: the uint8 buffer holds image
+ *   rows [band_top, band_top + band_h) as for s2s_stain_quant_u8.  tissue long [B] is ADDED to with integer atomics (the
+ *   caller zeroes it; the bands of a region add up in it).  What s2s_objects_label labels with fg_bits = 1. */
 int s2s_stain_quant_chunks(int cell_h, int cell_w);
 int s2s_stain_quant_u8(const void* a, long pitch_a, long img_a, const void* b, long pitch_b, long img_b, int paired,
                        int B, int band_top, int band_h, int H, int W, int cell_h, int cell_w, int g0, int ng,
@@ -451,6 +455,11 @@ int s2s_stain_quant_finalize(const double* part, long owners, int nchunk, int pa
                              float* out, void* stream);
 int s2s_stain_separate(const void* img, int is_f32, long pitch, long img_stride, int B, int H, int W,
                        const float* od_table, const float* unmix, float* out, void* stream);
+int s2s_stain_mask_u8(const void* img, long pitch, long img_stride, int B, int band_top, int band_h, int H, int W,
+                      const float* od_table, const float* unmix, int white, int black, int stain, void* mask,
+                      long mask_pitch, long mask_stride, long* tissue, void* stream);
+int s2s_stain_mask_f32(const float* img, int B, int H, int W, const float* od_table, const float* unmix, int white,
+                       int black, int stain, void* mask, long mask_pitch, long mask_stride, long* tissue, void* stream);
 
 /* ---- Macenko stain normalisation (stain_norm.hip) --------------------------------
  * The uint8 buffers hold image rows [band_top, band_top + band_h) of B images of H x W RGB pixels; pitch and img_stride
@@ -484,6 +493,40 @@ int s2s_stain_conc_hist_u8(const void* img, long pitch, long img_stride, int B, 
                            void* stream);
 int s2s_stain_normalize_u8(const void* img, long pitch, long img_stride, int B, int H, int W, const float* od_table,
                            const float* coef, void* out, long out_pitch, long out_img, int out_f32, void* stream);
+
+/* ---- stain object analysis: connected-component labelling (objects.hip) -----------
+ * A sample is H x W <= 2^31 - 2 pixels and has an index space of its own: nothing joins two samples.  B <= 65535.
+ * s2s_objects_words(B, H, W): the int32 words of scratch s2s_objects_label needs (parents, then chunk counts);
+ *   s2s_objects_hit_words: those of s2s_objects_hits.  Negative: a status code.
+ * s2s_objects_label: mask bytes [B][H][.] (pitch, img_stride in bytes), foreground iff (byte & fg_bits) != 0;
+ *   connectivity 4 or 8.  An object is kept iff its area >= min_area; kept objects are numbered 1..count[n] in raster
+ *   order of their first pixel.  labels int [B][H][W]: the number, 0 for background and dropped objects.  count int [B]
+ *   is written; kept_pixels long [B], largest int [B] and size_hist long [B][32] (bin floor(log2(area))) are ADDED to /
+ *   maxed into with integer atomics: the caller zeroes them.  max_objects > 0: rows < min(count, max_objects) of
+ *   tab_area int [B][M], tab_bbox int [B][M][4] (y0, x0, y1, x1, end-exclusive) and tab_sums long [B][M][2] (sum of y,
+ *   sum of x) are written, the other rows are not touched (the caller zeroes the tables).  max_objects == 0: no table,
+ *   the three pointers are ignored.  Nine launches, no host synchronisation.
+ * s2s_objects_centroid: centroid float [B][M][2] = float((double)sum / area) for rows < count, 0 beyond.
+ * s2s_objects_hits: hits int [B][2] = the objects of labels_pred that share a pixel with an object of labels_target, and
+ *   the other way round (per-object bit flags in scratch set by atomicOr, then counted).  Both are written.
+ * s2s_objects_scores: out float [B][3] = recall = hits_target / count_target, precision = hits_pred / count_pred (a
+ *   ratio whose count is 0 is 1 when the other count is 0 too, else 0), f1 = 2 p r / (p + r) (0 when p + r = 0), each
+ *   evaluated in double and rounded once; abs_err int [B] = |count_pred - count_target|.
+ * s2s_objects_density: burden float [B] = float((double)kept / max(tissue, 1)).  mm2_per_pixel: a HOST double
+ *   (mpp^2 * 1e-6), or null; given, per_mm2 double [B] = count / (tissue * mm2_per_pixel), 0 when tissue is 0. */
+long s2s_objects_words(int B, int H, int W);
+long s2s_objects_hit_words(int B, int H, int W);
+int s2s_objects_label(const void* mask, long pitch, long img_stride, int fg_bits, int B, int H, int W, int connectivity,
+                      int min_area, int max_objects, int* scratch, int* labels, int* count, long* kept_pixels,
+                      int* largest, long* size_hist, int* tab_area, int* tab_bbox, long* tab_sums, void* stream);
+int s2s_objects_centroid(const int* count, const int* tab_area, const long* tab_sums, int B, int max_objects,
+                         float* centroid, void* stream);
+int s2s_objects_hits(const int* labels_pred, const int* labels_target, int B, int H, int W, int* scratch, int* hits,
+                     void* stream);
+int s2s_objects_scores(const int* count_pred, const int* count_target, const int* hits, int B, float* out,
+                       int* abs_err, void* stream);
+int s2s_objects_density(const long* kept_pixels, const long* tissue, const int* count, int B,
+                        const double* mm2_per_pixel, float* burden, double* per_mm2, void* stream);
 
 /* ---- loss variants and class conditioning (loss_variants.hip) -- SURVEY section 8 row f4 -----------------
  * ROI-weighted MSE (conditional_flow_matching_masked.py:76-90): w = 1 + roi_lambda * mask,

@@ -26,6 +26,7 @@ from .image_metrics import generation_quality, image_quality, plan_bands, region
 from .stain_quant import (region_stain_agreement, region_stain_map, stain_agreement, stain_matrix, stain_quantify,
                           stain_separate)
 from .stain_norm import REFERENCE_HE, StainFit, fit_stains, normalize_region, stain_normalize
+from .objects import label_components, region_stain_objects, stain_object_agreement, stain_objects
 
 __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeEmbedding", "FlowUNet",
            "ConditionalFlowMatcher", "ConditionalFlowMatchingModule", "MultiTaskFlowMatchingModule", "euler_generate", "dopri5_generate", "euler_integrate", "dopri5_integrate", "SolverConfig", "GraphedVelocity",
@@ -36,4 +37,5 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "EvalAccumulator", "plan_tiles", "translate_region", "tissue_counts", "plan_region_batches", "multitask_sampler", "FIXED_STEP_METHODS",
            "fixed_step_generate", "fixed_step_integrate", "image_quality", "region_quality", "generation_quality",
            "plan_bands", "stain_matrix", "stain_quantify", "stain_agreement", "stain_separate", "region_stain_map",
-           "region_stain_agreement", "fit_stains", "stain_normalize", "normalize_region", "StainFit", "REFERENCE_HE"]
+           "region_stain_agreement", "fit_stains", "stain_normalize", "normalize_region", "StainFit", "REFERENCE_HE",
+           "label_components", "stain_objects", "stain_object_agreement", "region_stain_objects"]

@@ -9,6 +9,8 @@
 //   s2s_stain_quant_finalize  partials -> int64 counts, fp64 sums, fp32 burdens / mean ODs (single) or burdens, their
 //                             absolute difference, Dice and IoU of the positive masks (paired)
 //   s2s_stain_separate        uint8 or fp32 in, fp32 [B][3][H][W] concentrations out
+//   s2s_stain_mask_u8 / _f32  the positive mask of one stain as bytes: bit 0 = positive, bit 1 = tissue; the tissue count
+//                             per sample on the side (what objects.hip labels)
 //
 // Definition.  od(u) = -log10(max(u, 1) / 255) comes from a 256-entry fp32 table the host computes in double (no device
 // log); the table lives in LDS.  c_k = ((od_r * m_rk) + (od_g * m_gk)) + (od_b * m_bk), every product and sum rounded on
@@ -121,6 +123,9 @@ __device__ __forceinline__ float sq_conc(const SqParams& p, float odr, float odg
   return s + pb;
 }
 
+// THE rule: positive for stain k iff tissue and c_k > thr_k (every kernel here decides through this one statement)
+__device__ __forceinline__ int sq_positive(const SqParams& p, int t, float c, int k) { return (t && c > p.thr[k]) ? 1 : 0; }
+
 __device__ __forceinline__ void sq_table_to_lds(const SqParams& p, float* lut) {
   lut[threadIdx.x] = p.od[threadIdx.x];        // 256 lanes, 256 entries
   __syncthreads();
@@ -168,7 +173,7 @@ __global__ __launch_bounds__(256) void sq_reduce_kernel(const SqParams p, double
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
             const float c = sq_conc(p, odr, odg, odb, k);
-            ci[1 + k] += (t && c > p.thr[k]) ? 1 : 0;
+            ci[1 + k] += sq_positive(p, t, c, k);
             cd[k] += t ? (double)fmaxf(c, 0.0f) : 0.0;
           }
         } else {
@@ -176,7 +181,7 @@ __global__ __launch_bounds__(256) void sq_reduce_kernel(const SqParams p, double
           const int t2 = is_tissue(r2, g2, b2, p.white, p.black);
           const int k = p.stain;
           const float ca = sq_conc(p, odr, odg, odb, k), cb = sq_conc(p, lut[r2], lut[g2], lut[b2], k);
-          const int pa = (t && ca > p.thr[k]) ? 1 : 0, pb = (t2 && cb > p.thr[k]) ? 1 : 0;
+          const int pa = sq_positive(p, t, ca, k), pb = sq_positive(p, t2, cb, k);
           ci[0] += t;
           ci[1] += t2;
           ci[2] += pa & pb;
@@ -308,6 +313,59 @@ __global__ __launch_bounds__(256) void sq_separate_kernel(const SqParams p, int 
       }
     }
   }
+}
+
+// One thread per 4 consecutive pixels of one row: mask byte = positive | tissue << 1 for stain p.stain; tissue[n] += the
+// tissue pixels (an integer atomic per workgroup; the caller zeroes it, and the bands of a region add up in it).
+template <int LOADER>
+__global__ __launch_bounds__(256) void sq_mask_kernel(const SqParams p, int band_h, unsigned char* __restrict__ mask,
+                                                      long mpitch, long mimg, unsigned long long* tissue) {
+  __shared__ float lut[256];
+  __shared__ int red[4];
+  sq_table_to_lds(p, lut);
+  const int n = blockIdx.y, nq = (p.W + 3) >> 2, k = p.stain;
+  const long total = (long)band_h * nq;
+  int nt = 0;
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < total; q += (long)gridDim.x * 256) {
+    const int xq = (int)(q % nq), y = p.band_top + (int)(q / nq);
+    const int x0 = 4 * xq, px = min(4, p.W - x0);
+    unsigned v[12];
+    sq_load_quad<LOADER>(p.a, sq_row<LOADER>(p.img_a, p.pitch_a, n, y, p.band_top), p.chan, x0, px, v);
+    unsigned bytes = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j < px) {
+        const int t = is_tissue(v[3 * j], v[3 * j + 1], v[3 * j + 2], p.white, p.black);
+        const float c = sq_conc(p, lut[v[3 * j]], lut[v[3 * j + 1]], lut[v[3 * j + 2]], k);
+        bytes |= (unsigned)(sq_positive(p, t, c, k) | (t << 1)) << (8 * j);
+        nt += t;
+      }
+    }
+    unsigned char* o = mask + (long)n * mimg + (long)y * mpitch + x0;
+    if (px == 4 && ((uintptr_t)o & 3) == 0) {
+      *reinterpret_cast<unsigned*>(o) = bytes;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (j < px) o[j] = (unsigned char)(bytes >> (8 * j));
+      }
+    }
+  }
+  nt = wave_sum_i(nt);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = nt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int s = red[0] + red[1] + red[2] + red[3];
+    if (s) atomicAdd(tissue + n, (unsigned long long)s);
+  }
+}
+
+template <int LOADER>
+void sq_mask_launch(const SqParams& p, int B, int band_h, void* mask, long mpitch, long mimg, long* tissue, hipStream_t s) {
+  long blocks = ((long)band_h * cdiv(p.W, 4) + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(sq_mask_kernel<LOADER>, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, s, p, band_h,
+                     (unsigned char*)mask, mpitch, mimg, (unsigned long long*)tissue);
 }
 
 int sq_fill(SqParams& p, int H, int W, int cell_h, int cell_w, const float* od_table, const float* unmix, int white,
@@ -442,6 +500,43 @@ extern "C" int s2s_stain_separate(const void* img, int is_f32, long pitch, long 
   if (blocks > 16384) blocks = 16384;
   if (is_f32) hipLaunchKernelGGL(sq_separate_kernel<SQ_F32>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, B, out);
   else hipLaunchKernelGGL(sq_separate_kernel<SQ_U8>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, B, out);
+  S2S_LAUNCH_CHECK();
+  return S2S_OK;
+}
+
+extern "C" int s2s_stain_mask_u8(const void* img, long pitch, long img_stride, int B, int band_top, int band_h, int H,
+                                 int W, const float* od_table, const float* unmix, int white, int black, int stain,
+                                 void* mask, long mask_pitch, long mask_stride, long* tissue, void* stream) {
+  if (!img || !mask || !tissue) return S2S_ERR_NULL;
+  if (B < 1 || B > 65535) return S2S_ERR_SHAPE;
+  SqParams p;
+  const int rc = sq_fill(p, H, W, H, W, od_table, unmix, white, black, stain);
+  if (rc != S2S_OK) return rc;
+  if (pitch < 3L * W || mask_pitch < W || band_top < 0 || band_h < 1 || (long)band_top + band_h > H) return S2S_ERR_SHAPE;
+  if (B > 1 && (img_stride < pitch * (long)band_h || mask_stride < mask_pitch * (long)H)) return S2S_ERR_SHAPE;
+  p.a = img;
+  p.pitch_a = pitch;
+  p.img_a = img_stride;
+  p.band_top = band_top;
+  sq_mask_launch<SQ_U8>(p, B, band_h, mask, mask_pitch, mask_stride, tissue, (hipStream_t)stream);
+  S2S_LAUNCH_CHECK();
+  return S2S_OK;
+}
+
+extern "C" int s2s_stain_mask_f32(const float* img, int B, int H, int W, const float* od_table, const float* unmix,
+                                  int white, int black, int stain, void* mask, long mask_pitch, long mask_stride,
+                                  long* tissue, void* stream) {
+  if (!img || !mask || !tissue) return S2S_ERR_NULL;
+  if (B < 1 || B > 65535) return S2S_ERR_SHAPE;
+  SqParams p;
+  const int rc = sq_fill(p, H, W, H, W, od_table, unmix, white, black, stain);
+  if (rc != S2S_OK) return rc;
+  if (mask_pitch < W || (B > 1 && mask_stride < mask_pitch * (long)H)) return S2S_ERR_SHAPE;
+  p.a = img;
+  p.pitch_a = W;
+  p.chan = (long)H * W;
+  p.img_a = 3L * H * W;
+  sq_mask_launch<SQ_F32>(p, B, H, mask, mask_pitch, mask_stride, tissue, (hipStream_t)stream);
   S2S_LAUNCH_CHECK();
   return S2S_OK;
 }
