@@ -528,6 +528,29 @@ int s2s_objects_scores(const int* count_pred, const int* count_target, const int
 int s2s_objects_density(const long* kept_pixels, const long* tissue, const int* count, int B,
                         const double* mm2_per_pixel, float* burden, double* per_mm2, void* stream);
 
+/* ---- fused paired augmentation: crop, D4, stain jitter, masks (augment.hip) --------
+ * Geometry: params is a DEVICE int [B][param_cols], param_cols 4 or 5 = (top, left, hflip, vflip[, transpose]); with
+ *   f[a][b] = img[n][top + (vflip ? S-1-a : a)][left + (hflip ? S-1-b : b)], out[y][x] = transpose ? f[x][y] : f[y][x].
+ *   The same geometry applies to source, target and mask.  The caller validates the windows; the kernel does not clamp.
+ * Pixel map: a DEVICE float [B][12] per image kind = A[3][3] row-major, then b[3]; od_table is the HOST table of the
+ *   stain entry points.  od'_c = ((od_r A[0][c] + od_g A[1][c]) + od_b A[2][c]) + b[c], every operation rounded on its
+ *   own; u'_c = clamp(rint(255 * exp2(od'_c * -log2(10))), 0, 255).  white in 0..255: a pixel with min(R, G, B) >= white
+ *   keeps its bytes; -1: off.  A null map: the bytes pass unchanged.
+ * s2s_paired_augment: src / tgt uint8 [B][Hs][Ws][3], mask (optional) uint8 [B][Hs][Ws], each with a row pitch and an
+ *   image stride in bytes.  out_src / out_tgt float [B][3][S][S] = (u' / 255 - 0.5) / 0.5.  mask_kind 0: no mask (mask_u8
+ *   and out_mask null); 1 / 2 / 3: out_mask float / uint8 / int64 [B][1][S][S], the byte's value.  out_src_u8 /
+ *   out_tgt_u8 (each optional): uint8 [B][S][S][3], the augmented bytes.  One launch.
+ * s2s_stain_augment_u8: the pixel map alone on uint8 [B][H][W][3], any H and W.  out_f32 == 0: uint8 [B][H][W][3] with
+ *   out_pitch / out_img in bytes; else float [B][3][H][W] (out_pitch, out_img ignored).  One launch. */
+int s2s_paired_augment(const void* src_u8, long src_pitch, long src_img, const void* tgt_u8, long tgt_pitch,
+                       long tgt_img, const void* mask_u8, long mask_pitch, long mask_img, int B, int Hs, int Ws, int S,
+                       const int* params, int param_cols, const float* src_map, const float* tgt_map,
+                       const float* od_table, int white, float* out_src, float* out_tgt, void* out_mask, int mask_kind,
+                       void* out_src_u8, void* out_tgt_u8, void* stream);
+int s2s_stain_augment_u8(const void* img, long pitch, long img_stride, int B, int H, int W, const float* maps,
+                         const float* od_table, int white, void* out, long out_pitch, long out_img, int out_f32,
+                         void* stream);
+
 /* ---- loss variants and class conditioning (loss_variants.hip) -- SURVEY section 8 row f4 -----------------
  * ROI-weighted MSE (conditional_flow_matching_masked.py:76-90): w = 1 + roi_lambda * mask,
  *   out[0] = sum(w (v-u)^2) / (sum(w) + 1e-8), w broadcast over C.  v, u: float[B][C][HW]; mask: float[B][HW];

@@ -27,6 +27,8 @@ from .stain_quant import (region_stain_agreement, region_stain_map, stain_agreem
                           stain_separate)
 from .stain_norm import REFERENCE_HE, StainFit, fit_stains, normalize_region, stain_normalize
 from .objects import label_components, region_stain_objects, stain_object_agreement, stain_objects
+from .augment import (PairedAugmenter, paired_augment, sample_d4_params, sample_stain_jitter, stain_augment,
+                      stain_jitter_maps)
 
 __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeEmbedding", "FlowUNet",
            "ConditionalFlowMatcher", "ConditionalFlowMatchingModule", "MultiTaskFlowMatchingModule", "euler_generate", "dopri5_generate", "euler_integrate", "dopri5_integrate", "SolverConfig", "GraphedVelocity",
@@ -38,4 +40,6 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "fixed_step_generate", "fixed_step_integrate", "image_quality", "region_quality", "generation_quality",
            "plan_bands", "stain_matrix", "stain_quantify", "stain_agreement", "stain_separate", "region_stain_map",
            "region_stain_agreement", "fit_stains", "stain_normalize", "normalize_region", "StainFit", "REFERENCE_HE",
-           "label_components", "stain_objects", "stain_object_agreement", "region_stain_objects"]
+           "label_components", "stain_objects", "stain_object_agreement", "region_stain_objects",
+           "paired_augment", "stain_augment", "stain_jitter_maps", "sample_d4_params", "sample_stain_jitter",
+           "PairedAugmenter"]
