@@ -574,14 +574,17 @@ int s2s_class_embed_bwd(const float* dout, const long* y, float* dtable, int acc
  * nn.LeakyReLU(slope) (slope 0 = ReLU), NHWC with a pixel stride, C % 8 == 0.
  * work: float[2*B*C*s2s_instnorm_blocks()] for the forward, that + 2*B*C for the backward.
  * stats: float[4][B][C] = mean, 1/std, scale, shift; written by the forward, read by the backward.
- * backward: dx = d/dx of sum(g * y); dgamma/dbeta (both or neither) receive or accumulate the affine gradients. */
+ * backward: dx = d/dx of sum(g * y); dgamma/dbeta (both or neither) receive or accumulate the affine gradients.  x and
+ * eps are the forward's: the fp32 single-launch form (no dgamma, at most 32 x 32) takes mean and 1/std again from x in
+ * fp64 -- on a map of a few pixels dx is what a cancellation down to eps / (var + eps) leaves, beyond an fp32 1/std -- and
+ * reads stats only for the sign of z and the scale; every other form reads mean and 1/std from stats and ignores eps. */
 int s2s_instnorm_blocks(int B, int H, int W, int C);
 int s2s_instnorm_lrelu_fwd(int dtype, const void* x, int ldx, const float* gamma, const float* beta, void* y, int ldy,
                            float* work, float* stats, int B, int H, int W, int C, float eps, float slope,
                            void* stream);
 int s2s_instnorm_lrelu_bwd(int dtype, const void* g, int ldg, const void* x, int ldx, const float* stats, void* dx,
                            int lddx, float* dgamma, float* dbeta, int accumulate, float* work, int B, int H, int W,
-                           int C, float slope, void* stream);
+                           int C, float eps, float slope, void* stream);
 
 /* ---- 2x2-tap convolution on the MFMA loop (conv3x3_mfma.hip) -----------------------------------------
  * Row a13 again (no reference line to replace): nn.Conv2d(k=4, stride=2, padding=1) of a pix2pix
@@ -652,12 +655,17 @@ int s2s_convkxk_wgrad_nhwc(int dtype, const void* dy, int lddy, int Cout, const 
  * s2s_convt4x4s2_nhwc is the transposed layer / the convolution's data gradient by sub-pixel phase, x [B][h][w][Cin] ->
  * PLAIN y [B][2h][2w][C] (C % 64 == 0), wd = the data-gradient operand of s2s_pack_conv4x4.  kwork (optional):
  * float[..._ksplit()][output pixels][channels] for the split-K form of the small maps.  The weight gradient takes the
- * plain tensor with x_plain = 1 in s2s_convkxk_wgrad_nhwc (cin = 4 C stays the virtual channel count). */
+ * plain tensor with x_plain = 1 in s2s_convkxk_wgrad_nhwc (cin = 4 C stays the virtual channel count).
+ * s2s_conv4x4s2_plan / s2s_convt4x4s2_plan (host only): the launch plan such a call takes when it is given kwork, 0..5 =
+ * the tile plans 8x32x128, 8x32x64, 4x32x128, 4x32x64, 8x16x128, 8x16x64 (rows x columns x channels of one workgroup),
+ * 6 = the flat form of the power-of-two maps up to 8 x 8; a negative status for bad arguments. */
 int s2s_conv4x4s2_ksplit(int B, int H, int W, int Cout, int Cin);
+int s2s_conv4x4s2_plan(int B, int H, int W, int Cout, int Cin);
 int s2s_conv4x4s2_nhwc(int dtype, const void* x, int ldx, int Cin, const void* wf, const float* bias, void* y, int ldy,
                        void* y2, int ldy2, int act, float act_slope, float* kwork, int B, int H, int W, int Cout,
                        void* stream);
 int s2s_convt4x4s2_ksplit(int B, int h, int w, int C, int Cin);
+int s2s_convt4x4s2_plan(int B, int h, int w, int C, int Cin);
 int s2s_convt4x4s2_nhwc(int dtype, const void* x, int ldx, int Cin, const void* wd, const float* bias, void* y, int ldy,
                         float* kwork, int B, int h, int w, int C, void* stream);
 /* The same two layers on the generator's INNER levels as ONE launch with what follows them (conv_small.hip; bf16):
@@ -684,7 +692,7 @@ int s2s_instnorm_lrelu_fwd2(int dtype, const void* x, int ldx, const float* gamm
                             float slope, void* stream);
 int s2s_instnorm_lrelu_bwd2(int dtype, const void* g, int ldg, const void* g2, int ldg2, const void* x, int ldx,
                             const float* stats, void* dx, int lddx, float* dgamma, float* dbeta, int accumulate,
-                            float* work, int B, int H, int W, int C, float slope, void* stream);
+                            float* work, int B, int H, int W, int C, float eps, float slope, void* stream);
 /* The single-launch forms (bf16, no affine, maps of at most 32 x 32: s2s_instnorm_split_ok() != 0) with the input folded
  * from a split-K convolution's partial slabs, float[S][B*H*W][C] as s2s_conv4x4s2_nhwc / s2s_convt4x4s2_nhwc leave them in
  * kwork when called with y == NULL -- one launch instead of reduce + norm, bit-identical to the two-launch form.

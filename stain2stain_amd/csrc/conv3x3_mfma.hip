@@ -2834,12 +2834,25 @@ static int s2_ksplit(long base, int nchunk) {
   return sp < 2 ? 1 : (int)sp;
 }
 
+// The launch plan of the two entry points below, decided once: 0..5 = the s2_tile() index, 6 = the flat form (which needs
+// the split-K workspace: without one the tiled form runs).  The launchers switch on it; s2s_conv4x4s2_plan /
+// s2s_convt4x4s2_plan report it for a caller that passes a workspace, as the *_ksplit queries count for one.
+static int s2_plan(int B, int H, int W, int C, int mult, int nchunk, bool kwork) {
+  if (kwork && s2_flat_ok(H, W, nchunk)) return 6;
+  return s2_tile(B, H, W, C, mult, nullptr);
+}
+
 extern "C" int s2s_conv4x4s2_ksplit(int B, int H, int W, int Cout, int Cin) {
   if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Cin <= 0) return S2S_ERR_SHAPE;
   if (s2_flat_ok(H, W, cdiv(4 * Cin, 32))) return s2_flat_ksplit(B, H, W, Cout, 1, cdiv(4 * Cin, 32));
   long base;
   s2_tile(B, H, W, Cout, 1, &base);
   return s2_ksplit(base, cdiv(4 * Cin, 32));
+}
+
+extern "C" int s2s_conv4x4s2_plan(int B, int H, int W, int Cout, int Cin) {
+  if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Cin <= 0) return S2S_ERR_SHAPE;
+  return s2_plan(B, H, W, Cout, 1, cdiv(4 * Cin, 32), true);
 }
 
 extern "C" int s2s_conv4x4s2_nhwc(int dtype, const void* x, int ldx, int Cin, const void* wf, const float* bias, void* y,
@@ -2866,11 +2879,11 @@ extern "C" int s2s_conv4x4s2_nhwc(int dtype, const void* x, int ldx, int Cin, co
   a.kpart = a.ksplit > 1 ? kwork : nullptr;
   hipStream_t s = static_cast<hipStream_t>(stream);
   int rc;
-  if (a.kpart && s2_flat_ok(H, W, a.nchunk)) {
-    a.lgh = __builtin_ctz((unsigned)H); a.lgw = __builtin_ctz((unsigned)W);
-    rc = Cout > 64 ? launch_convflat<128, 1>(a, s) : launch_convflat<64, 1>(a, s);
-  } else
-  switch (s2_tile(B, H, W, Cout, 1, nullptr)) {
+  switch (s2_plan(B, H, W, Cout, 1, a.nchunk, a.kpart != nullptr)) {
+    case 6:
+      a.lgh = __builtin_ctz((unsigned)H); a.lgw = __builtin_ctz((unsigned)W);
+      rc = Cout > 64 ? launch_convflat<128, 1>(a, s) : launch_convflat<64, 1>(a, s);
+      break;
     case 0: rc = launch_convkxk<8, 32, 128, 2, 2, 2, 0, 1>(a, s); break;
     case 1: rc = launch_convkxk<8, 32, 64, 4, 1, 2, 0, 1>(a, s); break;
     case 2: rc = launch_convkxk<4, 32, 128, 2, 2, 2, 0, 1>(a, s); break;
@@ -2895,6 +2908,11 @@ extern "C" int s2s_convt4x4s2_ksplit(int B, int h, int w, int C, int Cin) {
   return s2_ksplit(base, cdiv(Cin, 32));
 }
 
+extern "C" int s2s_convt4x4s2_plan(int B, int h, int w, int C, int Cin) {
+  if (B <= 0 || h <= 0 || w <= 0 || C <= 0 || Cin <= 0) return S2S_ERR_SHAPE;
+  return s2_plan(B, h, w, C, 4, cdiv(Cin, 32), true);
+}
+
 extern "C" int s2s_convt4x4s2_nhwc(int dtype, const void* x, int ldx, int Cin, const void* wd, const float* bias, void* y,
                                    int ldy, float* kwork, int B, int h, int w, int C, void* stream) {
   const bool defer = !y;                                // as in s2s_conv4x4s2_nhwc
@@ -2915,11 +2933,11 @@ extern "C" int s2s_convt4x4s2_nhwc(int dtype, const void* x, int ldx, int Cin, c
   a.kpart = a.ksplit > 1 ? kwork : nullptr;
   hipStream_t s = static_cast<hipStream_t>(stream);
   int rc;
-  if (a.kpart && s2_flat_ok(h, w, a.nchunk)) {
-    a.lgh = __builtin_ctz((unsigned)h); a.lgw = __builtin_ctz((unsigned)w);
-    rc = C > 64 ? launch_convflat<128, 2>(a, s) : launch_convflat<64, 2>(a, s);
-  } else
-  switch (s2_tile(B, h, w, C, 4, nullptr)) {
+  switch (s2_plan(B, h, w, C, 4, a.nchunk, a.kpart != nullptr)) {
+    case 6:
+      a.lgh = __builtin_ctz((unsigned)h); a.lgw = __builtin_ctz((unsigned)w);
+      rc = C > 64 ? launch_convflat<128, 2>(a, s) : launch_convflat<64, 2>(a, s);
+      break;
     case 0: rc = launch_convkxk<8, 32, 128, 2, 2, 2, 1, 2>(a, s); break;
     case 1: rc = launch_convkxk<8, 32, 64, 4, 1, 2, 1, 2>(a, s); break;
     case 2: rc = launch_convkxk<4, 32, 128, 2, 2, 2, 1, 2>(a, s); break;

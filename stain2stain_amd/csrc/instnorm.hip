@@ -215,65 +215,37 @@ __global__ __launch_bounds__(256) void in_lrelu_bwd_apply_kernel(const T* __rest
 constexpr int IN_SMALL_HW = 1024;
 constexpr int IN_CG = 32;                      // channels per workgroup: 4 pieces x 64 pixel lanes
 
-template <typename T, bool BWD>
-__global__ __launch_bounds__(256) void in_small_kernel(const T* __restrict__ x, int ldx, const T* __restrict__ g, int ldg,
-                                                       const T* __restrict__ g2, int ldg2, T* __restrict__ y, int ldy,
+template <typename T>
+__global__ __launch_bounds__(256) void in_small_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy,
                                                        T* __restrict__ y2, int ldy2, float* __restrict__ stats, int B, int HW,
                                                        int C, float eps, float slope) {
   constexpr int PCB = IN_CG / 8, WL = 256 / PCB;
   const int pc = threadIdx.x & (PCB - 1), wl = threadIdx.x / PCB;
   const int n = blockIdx.y, c8 = blockIdx.x * IN_CG + pc * 8;
   const bool live = c8 < C;
-  const long BC = (long)B * C, o = (long)n * C + c8;
+  const long BC = (long)B * C;
   const T* const xb = x + (long)n * HW * ldx + c8;
   __shared__ double red[2][WL][IN_CG + 1];
-  __shared__ float fin[4][IN_CG];               // forward: mean, invstd, scale, shift; backward: k1, k2 in rows 0, 1
-  float mu[8], is[8], sc[8], sh[8];
-  if (BWD && live) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { mu[k] = stats[o + k]; is[k] = stats[BC + o + k]; sc[k] = stats[2 * BC + o + k]; sh[k] = stats[3 * BC + o + k]; }
-  }
+  __shared__ float fin[4][IN_CG];               // mean, invstd, scale, shift
   float s1[8], s2[8], shift0[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) { s1[k] = 0.f; s2[k] = 0.f; shift0[k] = 0.f; }
-  if (live && !BWD) {
+  if (live) {
     // shifted sums: sum(x - K), sum((x - K)^2) with K = the channel's first pixel.  E[x^2] - mean^2 loses everything
     // when the spread of a small map is far below its level (a 2-pixel map with var ~ eps); shifting by a value of the
     // data removes that cancellation at no cost
     const f32x8 v0 = load8(xb);
 #pragma unroll
     for (int k = 0; k < 8; ++k) shift0[k] = v0.v[k];
-  }
-  if (live) {
     for (int p = wl; p < HW; p += WL) {
-      f32x8 v = load8(xb + (long)p * ldx);
-      if (!BWD) {
+      const f32x8 v = load8(xb + (long)p * ldx);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) v.v[k] -= shift0[k];
-      }
-      if (BWD) {
-        const f32x8 gv = load8(g + ((long)n * HW + p) * ldg + c8);
-        f32x8 gw;
-        if (g2) gw = load8(g2 + ((long)n * HW + p) * ldg2 + c8);
-        else {
-#pragma unroll
-          for (int k = 0; k < 8; ++k) gw.v[k] = 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const float dz = fmaf(v.v[k], sc[k], sh[k]) > 0.f ? gv.v[k] + gw.v[k] : slope * gv.v[k];
-          s1[k] += dz;
-          s2[k] = fmaf(dz, (v.v[k] - mu[k]) * is[k], s2[k]);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { s1[k] += v.v[k]; s2[k] = fmaf(v.v[k], v.v[k], s2[k]); }
-      }
+      for (int k = 0; k < 8; ++k) { const float d = v.v[k] - shift0[k]; s1[k] += d; s2[k] = fmaf(d, d, s2[k]); }
     }
   }
 #pragma unroll
   for (int k = 0; k < 8; ++k) { red[0][wl][pc * 8 + k] = (double)s1[k]; red[1][wl][pc * 8 + k] = (double)s2[k]; }
-  if (!BWD && wl == 0) {
+  if (wl == 0) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) fin[0][pc * 8 + k] = shift0[k];           // K per channel, read back by the finalising lane
   }
@@ -282,29 +254,92 @@ __global__ __launch_bounds__(256) void in_small_kernel(const T* __restrict__ x, 
     double a = 0.0, b = 0.0;
     for (int r = 0; r < WL; ++r) { a += red[0][r][threadIdx.x]; b += red[1][r][threadIdx.x]; }
     const int c = blockIdx.x * IN_CG + threadIdx.x;
-    if (BWD) {
-      fin[0][threadIdx.x] = (float)a / (float)HW;            // as the three-launch form: float sums, then * 1/HW
-      fin[1][threadIdx.x] = (float)b / (float)HW;
-    } else {
-      const double ms = a / (double)HW;                       // mean of the shifted values
-      double var = b / (double)HW - ms * ms;
-      if (var < 0.0) var = 0.0;
-      const double mean = ms + (double)fin[0][threadIdx.x];
-      const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-      fin[0][threadIdx.x] = (float)mean; fin[1][threadIdx.x] = invstd;
-      fin[2][threadIdx.x] = invstd; fin[3][threadIdx.x] = -(float)mean * invstd;
-      if (c < C) {
-        const long i = (long)n * C + c;
-        stats[i] = (float)mean; stats[BC + i] = invstd; stats[2 * BC + i] = invstd; stats[3 * BC + i] = -(float)mean * invstd;
-      }
+    const double ms = a / (double)HW;                       // mean of the shifted values
+    double var = b / (double)HW - ms * ms;
+    if (var < 0.0) var = 0.0;
+    const double mean = ms + (double)fin[0][threadIdx.x];
+    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
+    fin[0][threadIdx.x] = (float)mean; fin[1][threadIdx.x] = invstd;
+    fin[2][threadIdx.x] = invstd; fin[3][threadIdx.x] = -(float)mean * invstd;
+    if (c < C) {
+      const long i = (long)n * C + c;
+      stats[i] = (float)mean; stats[BC + i] = invstd; stats[2 * BC + i] = invstd; stats[3 * BC + i] = -(float)mean * invstd;
     }
   }
   __syncthreads();
   if (!live) return;
-  if (BWD) {
-    float k1[8], k2[8];
+  float fs[8], fh[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { k1[k] = fin[0][pc * 8 + k]; k2[k] = fin[1][pc * 8 + k]; }
+  for (int k = 0; k < 8; ++k) { fs[k] = fin[2][pc * 8 + k]; fh[k] = fin[3][pc * 8 + k]; }
+  for (int p = wl; p < HW; p += WL) {
+    const f32x8 v = load8(xb + (long)p * ldx);
+    f32x8 o8, r8;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float z = fmaf(v.v[k], fs[k], fh[k]);
+      o8.v[k] = z > 0.f ? z : slope * z;
+      r8.v[k] = fmaxf(z, 0.f);
+    }
+    store8(y + ((long)n * HW + p) * ldy + c8, o8);
+    if (y2) store8(y2 + ((long)n * HW + p) * ldy2 + c8, r8);
+  }
+}
+
+// Backward of the above (fp32 storage, the parity mode).  mean and 1/std are taken again from x in fp64, and
+// dx = scale * (dz - mean(dz) - xhat * mean(dz * xhat)) is evaluated in fp64 throughout: on a map of a few pixels
+// dz - mean(dz) is nearly collinear with xhat -- with two pixels exactly -- so dx is what a cancellation down to
+// eps / (var + eps) leaves, and the fp32 1/std of stats[] cannot carry that (2e-3 of max |dx| on a 1 x 2 map, as torch's
+// own fp32 autograd).  stats[] still decides the sign of z, exactly as the forward did, and gives the scale (gamma / std
+// where the forward was affine); x must be the tensor the statistics were taken from and eps the forward's.
+template <typename T>
+__global__ __launch_bounds__(256) void in_small_bwd_kernel(const T* __restrict__ x, int ldx, const T* __restrict__ g, int ldg,
+                                                           const T* __restrict__ g2, int ldg2, T* __restrict__ dx, int lddx,
+                                                           const float* __restrict__ stats, int B, int HW, int C, float eps,
+                                                           float slope) {
+  constexpr int PCB = IN_CG / 8, WL = 256 / PCB;
+  const int pc = threadIdx.x & (PCB - 1), wl = threadIdx.x / PCB;
+  const int n = blockIdx.y, c8 = blockIdx.x * IN_CG + pc * 8;
+  const bool live = c8 < C;
+  const long BC = (long)B * C, o = (long)n * C + c8;
+  const T* const xb = x + (long)n * HW * ldx + c8;
+  __shared__ double red[2][WL][IN_CG + 1];
+  __shared__ double fin[2][IN_CG];              // mean, 1/std; then mean(dz), mean(dz * xhat)
+  float is[8], sc[8], sh[8];
+  double a1[8], a2[8], mu[8], isd[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { a1[k] = 0.0; a2[k] = 0.0; mu[k] = 0.0; is[k] = 1.f; sc[k] = 0.f; sh[k] = 0.f; }
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { is[k] = stats[BC + o + k]; sc[k] = stats[2 * BC + o + k]; sh[k] = stats[3 * BC + o + k]; }
+    const f32x8 v0 = load8(xb);                  // the forward's shift, here with exact differences
+#pragma unroll
+    for (int k = 0; k < 8; ++k) mu[k] = (double)v0.v[k];
+    for (int p = wl; p < HW; p += WL) {
+      const f32x8 v = load8(xb + (long)p * ldx);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { const double d = (double)v.v[k] - mu[k]; a1[k] += d; a2[k] = fma(d, d, a2[k]); }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { red[0][wl][pc * 8 + k] = a1[k]; red[1][wl][pc * 8 + k] = a2[k]; }
+  if (wl == 0) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) fin[0][pc * 8 + k] = mu[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < IN_CG) {
+    double a = 0.0, b = 0.0;
+    for (int r = 0; r < WL; ++r) { a += red[0][r][threadIdx.x]; b += red[1][r][threadIdx.x]; }
+    const double ms = a / (double)HW;
+    double var = b / (double)HW - ms * ms;
+    if (var < 0.0) var = 0.0;
+    fin[0][threadIdx.x] = ms + fin[0][threadIdx.x];
+    fin[1][threadIdx.x] = 1.0 / sqrt(var + (double)eps);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { mu[k] = fin[0][pc * 8 + k]; isd[k] = fin[1][pc * 8 + k]; a1[k] = 0.0; a2[k] = 0.0; }
+  if (live) {
     for (int p = wl; p < HW; p += WL) {
       const f32x8 v = load8(xb + (long)p * ldx);
       const f32x8 gv = load8(g + ((long)n * HW + p) * ldg + c8);
@@ -314,30 +349,48 @@ __global__ __launch_bounds__(256) void in_small_kernel(const T* __restrict__ x, 
 #pragma unroll
         for (int k = 0; k < 8; ++k) gw.v[k] = 0.f;
       }
-      f32x8 o8;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        const float dz = fmaf(v.v[k], sc[k], sh[k]) > 0.f ? gv.v[k] + gw.v[k] : slope * gv.v[k];
-        o8.v[k] = sc[k] * (dz - k1[k] - ((v.v[k] - mu[k]) * is[k]) * k2[k]);
+        const double dz = fmaf(v.v[k], sc[k], sh[k]) > 0.f ? (double)gv.v[k] + (double)gw.v[k] : (double)slope * (double)gv.v[k];
+        a1[k] += dz;
+        a2[k] = fma(dz, ((double)v.v[k] - mu[k]) * isd[k], a2[k]);
       }
-      store8(y + ((long)n * HW + p) * ldy + c8, o8);
     }
-  } else {
-    float fs[8], fh[8];
+  }
+  __syncthreads();                               // every lane has read fin and the first pass's red
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { fs[k] = fin[2][pc * 8 + k]; fh[k] = fin[3][pc * 8 + k]; }
-    for (int p = wl; p < HW; p += WL) {
-      const f32x8 v = load8(xb + (long)p * ldx);
-      f32x8 o8, r8;
+  for (int k = 0; k < 8; ++k) { red[0][wl][pc * 8 + k] = a1[k]; red[1][wl][pc * 8 + k] = a2[k]; }
+  __syncthreads();
+  if (threadIdx.x < IN_CG) {
+    double a = 0.0, b = 0.0;
+    for (int r = 0; r < WL; ++r) { a += red[0][r][threadIdx.x]; b += red[1][r][threadIdx.x]; }
+    fin[0][threadIdx.x] = a / (double)HW;
+    fin[1][threadIdx.x] = b / (double)HW;
+  }
+  __syncthreads();
+  if (!live) return;
+  double k1[8], k2[8], f[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float z = fmaf(v.v[k], fs[k], fh[k]);
-        o8.v[k] = z > 0.f ? z : slope * z;
-        r8.v[k] = fmaxf(z, 0.f);
-      }
-      store8(y + ((long)n * HW + p) * ldy + c8, o8);
-      if (y2) store8(y2 + ((long)n * HW + p) * ldy2 + c8, r8);
+  for (int k = 0; k < 8; ++k) {
+    k1[k] = fin[0][pc * 8 + k]; k2[k] = fin[1][pc * 8 + k];
+    f[k] = (double)sc[k] * (isd[k] / (double)is[k]);          // gamma / std, with the fp64 1/std
+  }
+  for (int p = wl; p < HW; p += WL) {
+    const f32x8 v = load8(xb + (long)p * ldx);
+    const f32x8 gv = load8(g + ((long)n * HW + p) * ldg + c8);
+    f32x8 gw;
+    if (g2) gw = load8(g2 + ((long)n * HW + p) * ldg2 + c8);
+    else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) gw.v[k] = 0.f;
     }
+    f32x8 o8;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const double dz = fmaf(v.v[k], sc[k], sh[k]) > 0.f ? (double)gv.v[k] + (double)gw.v[k] : (double)slope * (double)gv.v[k];
+      o8.v[k] = (float)(f[k] * (dz - k1[k] - ((double)v.v[k] - mu[k]) * isd[k] * k2[k]));
+    }
+    store8(dx + ((long)n * HW + p) * lddx + c8, o8);
   }
 }
 
@@ -573,8 +626,8 @@ extern "C" int s2s_instnorm_lrelu_fwd2(int dtype, const void* x, int ldx, const 
       hipLaunchKernelGGL((in_small_res_kernel<false, false>), rg, dim3(512), 0, s, (const bf16_t*)x, ldx, (const bf16_t*)nullptr,
                          0, (const bf16_t*)nullptr, 0, (bf16_t*)y, ldy, (bf16_t*)y2, ldy2, stats, B, HW, C, eps, slope);
     else if (dtype == S2S_F32)
-      hipLaunchKernelGGL((in_small_kernel<float, false>), sg, dim3(256), 0, s, (const float*)x, ldx, (const float*)nullptr, 0,
-                         (const float*)nullptr, 0, (float*)y, ldy, (float*)y2, ldy2, stats, B, HW, C, eps, slope);
+      hipLaunchKernelGGL(in_small_kernel<float>, sg, dim3(256), 0, s, (const float*)x, ldx, (float*)y, ldy, (float*)y2, ldy2,
+                         stats, B, HW, C, eps, slope);
     else return S2S_ERR_DTYPE;
     S2S_LAUNCH_CHECK();
     return S2S_OK;
@@ -651,9 +704,10 @@ extern "C" int s2s_instnorm_lrelu_fwd(int dtype, const void* x, int ldx, const f
 }
 
 // g2 (optional): the gradient wrt the forward's second output relu(z); dz = z > 0 ? g + g2 : slope * g.
+// eps: the forward's; read by the fp32 single-launch form, which takes its statistics again in fp64 (in_small_bwd_kernel).
 extern "C" int s2s_instnorm_lrelu_bwd2(int dtype, const void* g, int ldg, const void* g2, int ldg2, const void* x, int ldx,
                                        const float* stats, void* dx, int lddx, float* dgamma, float* dbeta, int accumulate,
-                                       float* work, int B, int H, int W, int C, float slope, void* stream) {
+                                       float* work, int B, int H, int W, int C, float eps, float slope, void* stream) {
   if (!g || !x || !stats || !dx || !work) return S2S_ERR_NULL;
   if ((dgamma == nullptr) != (dbeta == nullptr)) return S2S_ERR_NULL;
   if (!in_args_ok(B, H, W, C, ldx, ldg) || (lddx % 8) || (g2 && (ldg2 % 8))) return S2S_ERR_SHAPE;
@@ -670,9 +724,8 @@ extern "C" int s2s_instnorm_lrelu_bwd2(int dtype, const void* g, int ldg, const 
                          (const bf16_t*)nullptr, 0, (bf16_t*)dx, lddx, (bf16_t*)nullptr, 0, const_cast<float*>(stats), B, HW, C,
                          0.f, slope);
     else if (dtype == S2S_F32)
-      hipLaunchKernelGGL((in_small_kernel<float, true>), sg, dim3(256), 0, s, (const float*)x, ldx, (const float*)g, ldg,
-                         (const float*)g2, ldg2, (float*)dx, lddx, (float*)nullptr, 0, const_cast<float*>(stats), B, HW, C,
-                         0.f, slope);
+      hipLaunchKernelGGL(in_small_bwd_kernel<float>, sg, dim3(256), 0, s, (const float*)x, ldx, (const float*)g, ldg,
+                         (const float*)g2, ldg2, (float*)dx, lddx, stats, B, HW, C, eps, slope);
     else return S2S_ERR_DTYPE;
     S2S_LAUNCH_CHECK();
     return S2S_OK;
@@ -700,9 +753,9 @@ extern "C" int s2s_instnorm_lrelu_bwd2(int dtype, const void* g, int ldg, const 
 
 extern "C" int s2s_instnorm_lrelu_bwd(int dtype, const void* g, int ldg, const void* x, int ldx, const float* stats,
                                       void* dx, int lddx, float* dgamma, float* dbeta, int accumulate, float* work,
-                                      int B, int H, int W, int C, float slope, void* stream) {
+                                      int B, int H, int W, int C, float eps, float slope, void* stream) {
   return s2s_instnorm_lrelu_bwd2(dtype, g, ldg, nullptr, 8, x, ldx, stats, dx, lddx, dgamma, dbeta, accumulate, work, B, H,
-                                 W, C, slope, stream);
+                                 W, C, eps, slope, stream);
 }
 
 // ---- space-to-depth of the zero-padded image and its inverse (row a13) -------------------------------------------

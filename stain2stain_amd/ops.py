@@ -1314,7 +1314,9 @@ def instnorm_lrelu_fwd(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Opt
 @_timed("instnorm_lrelu_bwd")
 def instnorm_lrelu_bwd(g: torch.Tensor, x: torch.Tensor, stats: torch.Tensor, slope: float = 0.2,
                        dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None,
-                       accumulate: bool = False) -> torch.Tensor:
+                       accumulate: bool = False, eps: float = 1e-5) -> torch.Tensor:
+    """dx (and dgamma / dbeta) of instnorm_lrelu_fwd; ``x`` and ``eps`` are the forward's (the fp32 small-map form takes its
+    statistics again from x in fp64)."""
     B, H, W, C = x.shape
     if g.shape != x.shape or g.dtype != x.dtype:
         raise RuntimeError("stain2stain_amd: instnorm_lrelu_bwd operand mismatch")
@@ -1325,7 +1327,7 @@ def instnorm_lrelu_bwd(g: torch.Tensor, x: torch.Tensor, stats: torch.Tensor, sl
     _native.check(min(nb, 0), "instnorm_blocks")
     work = torch.empty(2 * B * C * nb + 2 * B * C, dtype=torch.float32, device=x.device)
     rc = _L().s2s_instnorm_lrelu_bwd(_dt(x), pg, ldg, px, ldx, _f32(stats), dx.data_ptr(), C, _f32(dgamma), _f32(dbeta),
-                                     int(accumulate), _f32(work), B, H, W, C, slope, _stream())
+                                     int(accumulate), _f32(work), B, H, W, C, eps, slope, _stream())
     _native.check(rc, "instnorm_lrelu_bwd")
     return dx
 
@@ -1573,7 +1575,7 @@ def instnorm_lrelu_fwd2(x: torch.Tensor, slope: float, out: torch.Tensor, out2: 
 
 @_timed("instnorm_lrelu_bwd")
 def instnorm_lrelu_bwd2(g: torch.Tensor, g2: Optional[torch.Tensor], x: torch.Tensor, stats: torch.Tensor,
-                        slope: float) -> torch.Tensor:
+                        slope: float, eps: float = 1e-5) -> torch.Tensor:
     """dx of InstanceNorm + LeakyReLU for the gradients g (wrt the LeakyReLU output; a tensor or the ``SplitSum`` of the
     data gradient that produced it) and g2 (wrt the relu copy)."""
     B, H, W, C = x.shape
@@ -1592,7 +1594,7 @@ def instnorm_lrelu_bwd2(g: torch.Tensor, g2: Optional[torch.Tensor], x: torch.Te
     _native.check(min(nb, 0), "instnorm_blocks")
     work = torch.empty(2 * B * C * nb + 2 * B * C, dtype=torch.float32, device=x.device)
     rc = _L().s2s_instnorm_lrelu_bwd2(_dt(x), pg, ldg, p2, ld2, px, ldx, _f32(stats), dx.data_ptr(), C, 0, 0, 0,
-                                      _f32(work), B, H, W, C, slope, _stream())
+                                      _f32(work), B, H, W, C, eps, slope, _stream())
     _native.check(rc, "instnorm_lrelu_bwd2")
     return dx
 

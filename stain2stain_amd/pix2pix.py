@@ -23,7 +23,7 @@ class _InstNormLReLU(torch.autograd.Function):
         xs = x.permute(0, 2, 3, 1)                                   # NHWC view of a channels_last tensor
         y, stats = ops.instnorm_lrelu_fwd(xs, weight, bias, eps, slope)
         ctx.save_for_backward(xs, stats)
-        ctx.slope, ctx.affine = slope, weight is not None
+        ctx.slope, ctx.eps, ctx.affine = slope, eps, weight is not None
         return y.permute(0, 3, 1, 2)                                 # logical NCHW, channels_last memory
 
     @staticmethod
@@ -38,7 +38,7 @@ class _InstNormLReLU(torch.autograd.Function):
             C = xs.shape[3]
             dg = torch.empty(C, dtype=torch.float32, device=xs.device)
             db = torch.empty(C, dtype=torch.float32, device=xs.device)
-        dx = ops.instnorm_lrelu_bwd(g, xs, stats, ctx.slope, dg, db)
+        dx = ops.instnorm_lrelu_bwd(g, xs, stats, ctx.slope, dg, db, eps=ctx.eps)
         return dx.permute(0, 3, 1, 2), dg, db, None, None
 
 
