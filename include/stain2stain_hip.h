@@ -551,6 +551,35 @@ int s2s_stain_augment_u8(const void* img, long pitch, long img_stride, int B, in
                          const float* od_table, int white, void* out, long out_pitch, long out_img, int out_f32,
                          void* stream);
 
+/* ---- paired tile registration: integer-shift ZNCC search (registration.hip) --------
+ * uint8 images are addressed by pitch / img_stride in bytes; any pitch and any base alignment are accepted, and the
+ * samples of an input may interleave (the cells of one row of a region: img_stride = 3 * cell, pitch = 3 * W).
+ * s2s_structure_map_u8: img uint8 [B][H][W][3]; q_table HOST int [256] = rint(od(u) * 2^12); w HOST int [3] =
+ *   rint(unmix[ch][k] * gain * 16); acc = w_r q[R] + w_g q[G] + w_b q[B], f = clamp((acc + 2^15) >> 16, 0, 255)
+ *   (arithmetic shift); ds in {1, 2, 4}: out = (sum of the ds x ds block of f + ds^2 / 2) / ds^2 over whole blocks.
+ *   out uint8 [B][H / ds][W / ds], contiguous.  One launch.
+ * s2s_register_sums: a, b uint8 [B][h][w], contiguous; 0 <= R <= 32, S = 2 R + 1; center DEVICE int [B][2] = (cy, cx)
+ *   or null = 0.  my = R + |cy|, mx = R + |cx| in 64 bits; the template is a[my : h - my, mx : w - mx], the window of
+ *   shift (dy, dx) in centre + [-R, R]^2 is b[my + dy : h - my + dy, mx + dx : w - mx + dx].  tsum long [B][3] = n,
+ *   sum a, sum a^2; sums long [B][S][S][3] = sum b, sum b^2, sum a b; both are zeroed here.  A sample whose template is
+ *   empty keeps zeros and none of its pixels is read; no centre moves a read outside [0, h) x [0, w).  Shape status for
+ *   R > 32, h <= 2 R, w <= 2 R or (h - 2 R)(w - 2 R) > 2^18.  Two memsets and one launch.
+ * s2s_register_pick: va = n sum a^2 - (sum a)^2, vb alike, num = n sum a b - sum a sum b in int64; score = double(num) /
+ *   sqrt(double(va) * double(vb)), 0 when vb = 0.  Pick: highest score, then smallest (dy - cy)^2 + (dx - cx)^2, then
+ *   smallest dy, then smallest dx.  shift int [B][2] = (dy, dx) * ds; score double [B][3] = best, at the centre, best
+ *   minus the best outside the 3 x 3 neighbourhood of the peak (0 when R < 2); valid int [B]: 0 when n = 0 or va = 0,
+ *   and then shift = centre * ds clamped to int32 and the three scores are 0.  One launch.
+ * s2s_shift_tiles_u8: img uint8 [B][H][W][C], C = 1 or 3; shift DEVICE int [B][2] = (dy, dx), any values;
+ *   out[b][y][x] = img[b][y + dy][x + dx] inside the image, else fill (0..255).  One launch. */
+int s2s_structure_map_u8(const void* img, long pitch, long img_stride, int B, int H, int W, const int* q_table,
+                         const int* w, int ds, void* out, void* stream);
+int s2s_register_sums(const void* a, const void* b, int B, int h, int w, int R, const int* center, long* tsum,
+                      long* sums, void* stream);
+int s2s_register_pick(const long* tsum, const long* sums, const int* center, int B, int R, int ds, int* shift,
+                      double* score, int* valid, void* stream);
+int s2s_shift_tiles_u8(const void* img, long pitch, long img_stride, int B, int H, int W, int C, const int* shift,
+                       int fill, void* out, long out_pitch, long out_img, void* stream);
+
 /* ---- loss variants and class conditioning (loss_variants.hip) -- SURVEY section 8 row f4 -----------------
  * ROI-weighted MSE (conditional_flow_matching_masked.py:76-90): w = 1 + roi_lambda * mask,
  *   out[0] = sum(w (v-u)^2) / (sum(w) + 1e-8), w broadcast over C.  v, u: float[B][C][HW]; mask: float[B][HW];

@@ -29,6 +29,8 @@ from .stain_norm import REFERENCE_HE, StainFit, fit_stains, normalize_region, st
 from .objects import label_components, region_stain_objects, stain_object_agreement, stain_objects
 from .augment import (PairedAugmenter, paired_augment, sample_d4_params, sample_stain_jitter, stain_augment,
                       stain_jitter_maps)
+from .registration import (overlap_boxes, region_shift_field, register_pairs, registered_quality,
+                           sample_crop_params_within, shift_tiles, structure_map, structure_weights)
 
 __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeEmbedding", "FlowUNet",
            "ConditionalFlowMatcher", "ConditionalFlowMatchingModule", "MultiTaskFlowMatchingModule", "euler_generate", "dopri5_generate", "euler_integrate", "dopri5_integrate", "SolverConfig", "GraphedVelocity",
@@ -42,4 +44,5 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "region_stain_agreement", "fit_stains", "stain_normalize", "normalize_region", "StainFit", "REFERENCE_HE",
            "label_components", "stain_objects", "stain_object_agreement", "region_stain_objects",
            "paired_augment", "stain_augment", "stain_jitter_maps", "sample_d4_params", "sample_stain_jitter",
-           "PairedAugmenter"]
+           "PairedAugmenter", "structure_weights", "structure_map", "register_pairs", "shift_tiles", "overlap_boxes",
+           "sample_crop_params_within", "registered_quality", "region_shift_field"]
