@@ -186,6 +186,12 @@ int s2s_bn_relu_bwd_phase(int dtype, const void* g1, int ldg1, const void* gp, i
  * to the input first: x = bottleneck + t[:, :, None, None] (task_decoders.py:119-125). */
 int s2s_upsample2x_bilinear_ac_fwd(int dtype, const void* x, int ldx, const float* bias_nc, void* y, int ldy, int B,
                                    int Hin, int Win, int Hout, int Wout, int C, void* stream);
+/* test-facing: the row-sweep kernel that the production forward replaced; same arguments, same bits */
+int s2s_upsample2x_bilinear_ac_fwd_ref(int dtype, const void* x, int ldx, const float* bias_nc, void* y, int ldy, int B,
+                                       int Hin, int Win, int Hout, int Wout, int C, void* stream);
+/* test-facing, no launch: which forward kernel the shape takes (0 row sweep, 1 the register-window kernel; < 0 the
+ * launch's shape error); reference != 0: as the _ref entry point chooses */
+int s2s_upsample2x_fwd_family(int ldx, int ldy, int B, int Hin, int Win, int Hout, int Wout, int C, int reference);
 int s2s_upsample2x_bilinear_ac_bwd(int dtype, const void* dy, int lddy, void* dx, int lddx, int B, int Hin, int Win,
                                    int Hout, int Wout, int C, void* stream);
 /* test-facing: the per-pixel window kernel that the production backward replaced; same arguments, same bits */

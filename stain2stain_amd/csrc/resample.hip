@@ -29,12 +29,38 @@ __device__ __forceinline__ Axis ac_axis(int dst, int n_in, float scale) {
   return a;
 }
 
+// The forward kernels' axis: ac_axis with w1 = src - i0 taken as ONE fused multiply-subtract of scale * dst, which is what
+// the compiler made of it in the row-sweep kernel; a rounded product followed by a subtract (what it makes of the same
+// source inside another loop) differs in the last bit of the weight.  The indices are ac_axis's.
+__device__ __forceinline__ Axis ac_axis_fwd(int dst, int n_in, float scale) {
+  Axis a = ac_axis(dst, n_in, scale);
+  a.w1 = __builtin_fmaf(scale, (float)dst, -(float)a.i0);
+  a.w0 = 1.f - a.w1;
+  return a;
+}
+
+// One forward output, in two steps that both forward kernels compile from this source: the horizontal mix of one source
+// row (bias added per tap), then the vertical mix of two such rows.  A mix w0 * p + w1 * q rounds one product and
+// fuses the other into the add, and which one is which changes the last bit.  Left to the compiler the choice fell by
+// channel parity (it vectorised the row-sweep kernel two channels at a time and paired the products crosswise), and
+// differently again in another kernel.  The step's results are pinned to those bits, so the choice is written out:
+// channel k of a piece of 8 fuses w1 * q when k is even and w0 * p when k is odd.
+__device__ __forceinline__ float up_mix2(float w0, float p, float w1, float q, int k) {
+  return (k & 1) ? __builtin_fmaf(w0, p, w1 * q) : __builtin_fmaf(w1, q, w0 * p);
+}
+__device__ __forceinline__ float up_row_mix(const Axis& ax, float v0, float v1, float b, int k) {
+  return up_mix2(ax.w0, v0 + b, ax.w1, v1 + b, k);
+}
+__device__ __forceinline__ float up_col_mix(const Axis& ay, float h0, float h1, int k) {
+  return up_mix2(ay.w0, h0, ay.w1, h1, k);
+}
+
 // Thread layout (both directions): a workgroup owns one image row; lanes walk the channel pieces of a pixel first
 // (PCB pieces of 8 channels, so a wave touches whole NHWC pixel rows) and the remaining 256/PCB thread slots walk
 // the pixels of the row.  Row quantities (vertical tap and weights, row base pointers) are wave-uniform and there
 // is no per-element div/mod; the earlier flat-index kernels spent ~300 VALU instructions per 16 B and ran at a
 // third of the HBM rate.
-__device__ __forceinline__ int rs_pcb(int C) {
+__host__ __device__ __forceinline__ int rs_pcb(int C) {
   int p = 1;
   while (p < 32 && p * 8 < C) p <<= 1;
   return p;
@@ -61,7 +87,7 @@ __global__ __launch_bounds__(256) void upsample2x_fwd_kernel(const T* __restrict
     const int n = row / Hout, oy = row - n * Hout;
     const int uy = oy - padT;
     const bool row_in = uy >= 0 && uy < Hu;
-    const Axis ay = ac_axis(row_in ? uy : 0, Hin, sh);
+    const Axis ay = ac_axis_fwd(row_in ? uy : 0, Hin, sh);
     const T* const r0 = x + ((long)n * Hin + ay.i0) * Win * ldx;
     const T* const r1 = x + ((long)n * Hin + ay.i1) * Win * ldx;
     T* const yr = y + (long)row * Wout * ldy;
@@ -78,14 +104,13 @@ __global__ __launch_bounds__(256) void upsample2x_fwd_kernel(const T* __restrict
 #pragma unroll
           for (int k = 0; k < 8; ++k) o.v[k] = 0.f;
         } else {
-          const Axis ax = ac_axis(ux, Win, sw);
+          const Axis ax = ac_axis_fwd(ux, Win, sw);
           const int o0 = ax.i0 * ldx + c8, o1 = ax.i1 * ldx + c8;
           const f32x8 v00 = load8(r0 + o0), v01 = load8(r0 + o1), v10 = load8(r1 + o0), v11 = load8(r1 + o1);
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
             const float b = bv[k];
-            o.v[k] = ay.w0 * (ax.w0 * (v00.v[k] + b) + ax.w1 * (v01.v[k] + b)) +
-                     ay.w1 * (ax.w0 * (v10.v[k] + b) + ax.w1 * (v11.v[k] + b));
+            o.v[k] = up_col_mix(ay, up_row_mix(ax, v00.v[k], v01.v[k], b, k), up_row_mix(ax, v10.v[k], v11.v[k], b, k), k);
           }
         }
         store8(yr + ox * ldy + c8, o);
@@ -386,6 +411,146 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 2) void upsample2x_bwd_qu
   }
 }
 
+// Almost always output row 2a mixes source rows (a - 1, a) and row 2a + 1 rows (a, a + 1).  The first and last output row
+// of a map do not (their second tap is clamped or their first is row 0 itself), and whatever else ac_axis may round to
+// would not either: the kernel tests every pair, which is wave-uniform.
+__device__ __forceinline__ bool up_usual_pair(const Axis (&ay)[2], int a) {
+  const bool u = ay[0].i0 == a - 1 && ay[0].i1 == a && ay[1].i0 == a && ay[1].i1 == a + 1;
+  return __builtin_amdgcn_readfirstlane((int)u) != 0;
+}
+
+// The production forward for maps of 2 .. 4096 source pixels per axis: the same per-output expression as
+// upsample2x_fwd_kernel above (up_row_mix, up_col_mix, weights from ac_axis), with the vertical reuse held in registers.
+//
+// For n_in in 1..4096 outputs 2a and 2a + 1 of an axis read only source indices in [a - 1, a + 1]: i0 is a - 1 or a and
+// i1 <= a + 1 (checked exhaustively on the CPU with the kernel's fp32 arithmetic, tests/test_upsample_fwd_window_cpu.py).
+// A thread owns source column sx of one channel piece, i.e. output columns 2 sx and 2 sx + 1, and walks down the source
+// rows a = a0 .. a1 - 1 of its band.  For each source row it loads the four horizontal taps of its two output columns
+// (two of them usually name the same pixel) and mixes them horizontally once: that mix does not depend on the output
+// row.  The mixes of rows a - 1, a, a + 1 are what output rows 2a and 2a + 1 need, and two of the three carry over to
+// a + 1: one source row of loads per two output rows, where the kernel above loads two per output row, and every source
+// row is fetched once per band instead of once per output row.  The window is a matter of speed only: every pair is
+// tested (up_usual_pair) and one that does not fit it loads the rows its taps name, in a loop of its own after the walk
+// so that the walk's registers stay what the usual pair needs.
+//
+// A workgroup owns (sample, band of source rows, group of 256/PCB source columns, group of PCB channel pieces); lanes
+// walk channel pieces first.  Row taps and weights are wave-uniform.  A band re-reads one source row above and one below
+// it (its neighbours' rows); workgroup ids congruent mod 8 take a contiguous run of work items so those stay in one
+// XCD's L2.  The zero pad around the up-sampled image belongs to the threads at its edge: the first and last source
+// column take the pad columns, the first and last band take the pad rows.  Row bases are wave-uniform 64-bit pointers,
+// what a lane adds is an unsigned 32-bit byte offset (the host checks that a row's bytes fit).
+template <typename T>
+struct UpTaps { Raw8<T> t[2][2]; };          // one source row as loaded: [output column 2 sx + e][tap i0, i1]
+struct UpMix2 { f32x8 e[2]; };               // its horizontal mixes for output columns 2 sx and 2 sx + 1
+
+template <typename T, bool BIAS>
+__global__ __launch_bounds__(256, sizeof(T) == 2 && !BIAS ? 4 : 2) void upsample2x_fwd_win_kernel(
+    const T* __restrict__ x, int ldx, const float* __restrict__ bias, T* __restrict__ y, int ldy, int B, int Hin, int Win,
+    int Hout, int Wout, int padT, int padL, int C, int band, int nband, int ncol, int nwork) {
+  constexpr unsigned ES = sizeof(T);
+  const int cp = C >> 3;
+  const int Hu = 2 * Hin, Wu = 2 * Win;
+  const float sh = (float)(Hin - 1) / (float)(Hu - 1), sw = (float)(Win - 1) / (float)(Wu - 1);
+  const int PCB = rs_pcb(C), WL = 256 / PCB;
+  const int pc = threadIdx.x & (PCB - 1), slot = threadIdx.x / PCB;
+  // bijective deal of the workgroup ids: class b % 8 takes a contiguous run
+  const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, cls = blockIdx.x & 7;
+  const int wgid = (cls < r ? cls * (q + 1) : r * (q + 1) + (cls - r) * q) + (blockIdx.x >> 3);
+  const int chunk = wgid / nwork;                                     // channel group outermost
+  int work = wgid - chunk * nwork;
+  const int cg = work % ncol; work /= ncol;
+  const int bi = work % nband, n = work / nband;
+  const int a0 = bi * band, a1 = min(a0 + band, Hin);
+  const int sx = cg * WL + slot, piece = chunk * PCB + pc;
+  if (sx >= Win || piece >= cp) return;
+  const int c8 = piece * 8;
+
+  float bv[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) bv[k] = BIAS ? bias[(long)n * C + c8 + k] : 0.f;
+
+  const Axis ax[2] = {ac_axis_fwd(2 * sx, Win, sw), ac_axis_fwd(2 * sx + 1, Win, sw)};
+  const unsigned off[2][2] = {{(unsigned)(ax[0].i0 * ldx + c8) * ES, (unsigned)(ax[0].i1 * ldx + c8) * ES},
+                              {(unsigned)(ax[1].i0 * ldx + c8) * ES, (unsigned)(ax[1].i1 * ldx + c8) * ES}};
+  const int ox0 = padL + 2 * sx;
+  const unsigned yo[2] = {(unsigned)(ox0 * ldy + c8) * ES, (unsigned)((ox0 + 1) * ldy + c8) * ES};
+  const char* const xn = reinterpret_cast<const char*>(x + (long)n * Hin * Win * ldx);
+  char* const yn = reinterpret_cast<char*>(y + (long)n * Hout * Wout * ldy);
+  const long xrow = (long)Win * ldx * ES, yrow = (long)Wout * ldy * ES;
+
+  auto load_row = [&](int iy) {
+    const char* const rp = xn + min(max(iy, 0), Hin - 1) * xrow;
+    UpTaps<T> w;
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) w.t[e][t] = load_raw8(reinterpret_cast<const T*>(rp + off[e][t]));
+    return w;
+  };
+  auto mix_row = [&](const UpTaps<T>& w) {
+    UpMix2 m;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const f32x8 v0 = widen8(w.t[e][0]), v1 = widen8(w.t[e][1]);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) m.e[e].v[k] = up_row_mix(ax[e], v0.v[k], v1.v[k], bv[k], k);
+    }
+    return m;
+  };
+  auto put_row = [&](char* yr, const Axis& ay, const UpMix2& top, const UpMix2& bot) {
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+      f32x8 o;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o.v[k] = up_col_mix(ay, top.e[f].v[k], bot.e[f].v[k], k);
+      store8(reinterpret_cast<T*>(yr + yo[f]), o);
+    }
+  };
+
+  UpMix2 m0 = mix_row(load_row(a0 - 1)), m1 = mix_row(load_row(a0)), m2 = mix_row(load_row(a0 + 1));
+#pragma unroll 1
+  for (int a = a0; a < a1; ++a) {
+    // the next source row is on its way while this pair of output rows is mixed and stored (past the band's end it is
+    // the clamped row again, which nobody uses)
+    const UpTaps<T> nx = load_row(min(a + 2, a1));
+    const Axis ay[2] = {ac_axis_fwd(2 * a, Hin, sh), ac_axis_fwd(2 * a + 1, Hin, sh)};
+    if (up_usual_pair(ay, a)) {
+      char* const yr = yn + (padT + 2 * a) * yrow;
+      put_row(yr, ay[0], m0, m1);
+      put_row(yr + yrow, ay[1], m1, m2);
+    }
+    m0 = m1;
+    m1 = m2;
+    m2 = mix_row(nx);
+  }
+  // the pairs left out above load the rows that their taps name
+#pragma unroll 1
+  for (int a = a0; a < a1; ++a) {
+    const Axis ay[2] = {ac_axis_fwd(2 * a, Hin, sh), ac_axis_fwd(2 * a + 1, Hin, sh)};
+    if (up_usual_pair(ay, a)) continue;
+#pragma unroll 1
+    for (int e = 0; e < 2; ++e) {
+      const Axis ae = ac_axis_fwd(2 * a + e, Hin, sh);
+      const UpMix2 top = mix_row(load_row(ae.i0)), bot = mix_row(load_row(ae.i1));
+      put_row(yn + (padT + 2 * a + e) * yrow, ae, top, bot);
+    }
+  }
+
+  // the zero pad: columns left of the first and right of the last source column for this band's rows, and all of this
+  // thread's columns in the rows above the first and below the last band
+  const int zl = sx == 0 ? 0 : ox0, zr = sx == Win - 1 ? Wout : ox0 + 2;      // this thread's output columns [zl, zr)
+  const int ry0 = a0 == 0 ? 0 : padT + 2 * a0, ry1 = a1 == Hin ? Hout : padT + 2 * a1;      // and output rows
+  f32x8 zero;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) zero.v[k] = 0.f;
+  for (int oy = ry0; oy < ry1; ++oy) {
+    const bool pad_row = oy < padT || oy >= padT + Hu;
+    char* const yr = yn + oy * yrow;
+    for (int ox = zl; ox < zr; ++ox)
+      if (pad_row || ox < ox0 || ox >= ox0 + 2) store8(reinterpret_cast<T*>(yr + (unsigned)(ox * ldy + c8) * ES), zero);
+  }
+}
+
 // out[n][c] (+)= sum over the H*W pixels of x[n][.][.][c]   (gradient of the broadcast time bias)
 template <typename T>
 __global__ void pixel_sum_kernel(const T* __restrict__ x, int ldx, float* __restrict__ out, int HW, int C,
@@ -426,31 +591,101 @@ inline int ew_grid(long total) {
 
 }  // namespace
 
-extern "C" int s2s_upsample2x_bilinear_ac_fwd(int dtype, const void* x, int ldx, const float* bias_nc, void* y,
-                                              int ldy, int B, int Hin, int Win, int Hout, int Wout, int C,
-                                              void* stream) {
-  if (!x || !y) return S2S_ERR_NULL;
+namespace {
+
+// Which forward kernel a launch takes (s2s_upsample2x_fwd_family hands it to tests): the register-window kernel where
+// its window is proven (at most 4096 source pixels per axis), a map has at least two source pixels on both axes, a row's
+// bytes fit a 32-bit offset and the work-item count fits 32 bits; else the row-sweep kernel, which is also the test
+// reference.
+enum UpFwdFamily { kUpFwdRows = 0, kUpFwdWindow = 1 };
+
+// S2S_UP_BAND overrides either forward kernel's band (rows per work item); any value gives the same result
+int up_band_env() {
+  static const int band_env = [] { const char* e = getenv("S2S_UP_BAND"); return e ? atoi(e) : 0; }();
+  return band_env;
+}
+
+// source rows per work item of the register-window kernel: 8 where that leaves at least 2048 workgroups (8 per CU, two
+// rounds at 4 waves per SIMD), else 4 -- the fastest of 2 / 4 / 8 / 16 / 32 at each of the benchmark's four launches
+int upsample2x_fwd_band(int B, int Hin, int Win, int C) {
+  if (up_band_env() > 0) return up_band_env();
+  const long per_band = (long)B * cdiv(Win, 256 / rs_pcb(C)) * cdiv(C / 8, 32);
+  return per_band * cdiv(Hin, 8) >= 2048 ? 8 : 4;
+}
+
+int upsample2x_fwd_family(int ldx, int ldy, int B, int Hin, int Win, int Wout, int C, bool reference) {
+  if (reference || Hin < 2 || Win < 2 || Hin > 4096 || Win > 4096) return kUpFwdRows;
+  if ((long)Win * ldx >= (1L << 29) || (long)Wout * ldy >= (1L << 29)) return kUpFwdRows;   // 32-bit byte offsets in a row
+  const long nwg = (long)B * cdiv(Hin, upsample2x_fwd_band(B, Hin, Win, C)) * cdiv(Win, 256 / rs_pcb(C)) *
+                   cdiv(C / 8, 32);
+  return nwg < (1L << 31) ? kUpFwdWindow : kUpFwdRows;
+}
+
+int upsample2x_fwd_check(int ldx, int ldy, int B, int Hin, int Win, int Hout, int Wout, int C) {
   if (B <= 0 || Hin <= 0 || Win <= 0 || C <= 0 || (C % 8) || (ldx % 8) || (ldy % 8)) return S2S_ERR_SHAPE;
   if (Hout < 2 * Hin || Wout < 2 * Win) return S2S_ERR_SHAPE;  // F.pad with a negative size (crop) is not supported
-  const int padT = (Hout - 2 * Hin) / 2, padL = (Wout - 2 * Win) / 2;
   if ((long)Win * ldx >= (1L << 31) || (long)Wout * ldy >= (1L << 31) || (long)B * Hout >= (1L << 31))
     return S2S_ERR_SHAPE;                                        // 32-bit offsets inside a row
+  return S2S_OK;
+}
+
+// `reference`: the row-sweep kernel that the register-window kernel replaced (tests compare the two bit for bit)
+int upsample2x_fwd_launch(int dtype, const void* x, int ldx, const float* bias_nc, void* y, int ldy, int B, int Hin,
+                          int Win, int Hout, int Wout, int C, void* stream, bool reference) {
+  if (!x || !y) return S2S_ERR_NULL;
+  if (int rc = upsample2x_fwd_check(ldx, ldy, B, Hin, Win, Hout, Wout, C)) return rc;
+  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  const int padT = (Hout - 2 * Hin) / 2, padL = (Wout - 2 * Win) / 2;
   hipStream_t s = (hipStream_t)stream;
+  if (upsample2x_fwd_family(ldx, ldy, B, Hin, Win, Wout, C, reference) == kUpFwdWindow) {
+    const int band = upsample2x_fwd_band(B, Hin, Win, C), nband = cdiv(Hin, band);
+    const int ncol = cdiv(Win, 256 / rs_pcb(C)), nwork = B * nband * ncol;
+    const dim3 wgrid((unsigned)((long)nwork * cdiv(C / 8, 32)));
+#define S2S_UPW(TT, BB)                                                                                              \
+  hipLaunchKernelGGL((upsample2x_fwd_win_kernel<TT, BB>), wgrid, dim3(256), 0, s, (const TT*)x, ldx, bias_nc, (TT*)y, \
+                     ldy, B, Hin, Win, Hout, Wout, padT, padL, C, band, nband, ncol, nwork)
+    if (dtype == S2S_BF16) { if (bias_nc) S2S_UPW(bf16_t, true); else S2S_UPW(bf16_t, false); }
+    else { if (bias_nc) S2S_UPW(float, true); else S2S_UPW(float, false); }
+#undef S2S_UPW
+    S2S_LAUNCH_CHECK();
+    return S2S_OK;
+  }
   const long rows = (long)B * Hout;
   // rows per workgroup: 4 while that still leaves >= 1024 workgroups (4 per CU), else 2, else 1 (S2S_UP_BAND overrides)
-  static const int band_env = [] { const char* e = getenv("S2S_UP_BAND"); return e ? atoi(e) : 0; }();
-  const int band = band_env > 0 ? band_env : (rows >= 4096 ? 4 : rows >= 2048 ? 2 : 1);
+  const int band = up_band_env() > 0 ? up_band_env() : (rows >= 4096 ? 4 : rows >= 2048 ? 2 : 1);
   const long nwg = (rows + band - 1) / band;
   const dim3 grid((unsigned)(nwg < 65535 * 4 ? nwg : 65535 * 4));
 #define S2S_UP(TT, BB)                                                                                          \
   hipLaunchKernelGGL((upsample2x_fwd_kernel<TT, BB>), grid, dim3(256), 0, s, (const TT*)x, ldx, bias_nc, (TT*)y, \
                      ldy, B, Hin, Win, Hout, Wout, padT, padL, C, band)
   if (dtype == S2S_BF16) { if (bias_nc) S2S_UP(bf16_t, true); else S2S_UP(bf16_t, false); }
-  else if (dtype == S2S_F32) { if (bias_nc) S2S_UP(float, true); else S2S_UP(float, false); }
-  else return S2S_ERR_DTYPE;
+  else { if (bias_nc) S2S_UP(float, true); else S2S_UP(float, false); }
 #undef S2S_UP
   S2S_LAUNCH_CHECK();
   return S2S_OK;
+}
+
+}  // namespace
+
+extern "C" int s2s_upsample2x_bilinear_ac_fwd(int dtype, const void* x, int ldx, const float* bias_nc, void* y,
+                                              int ldy, int B, int Hin, int Win, int Hout, int Wout, int C,
+                                              void* stream) {
+  return upsample2x_fwd_launch(dtype, x, ldx, bias_nc, y, ldy, B, Hin, Win, Hout, Wout, C, stream, false);
+}
+
+// test-facing: the kernel the production entry point replaced, on the same arguments
+extern "C" int s2s_upsample2x_bilinear_ac_fwd_ref(int dtype, const void* x, int ldx, const float* bias_nc, void* y,
+                                                  int ldy, int B, int Hin, int Win, int Hout, int Wout, int C,
+                                                  void* stream) {
+  return upsample2x_fwd_launch(dtype, x, ldx, bias_nc, y, ldy, B, Hin, Win, Hout, Wout, C, stream, true);
+}
+
+// test-facing, no launch: 0 = row-sweep kernel, 1 = register-window kernel, < 0 = the shape error the launch would
+// return.  reference != 0: as s2s_upsample2x_bilinear_ac_fwd_ref chooses.
+extern "C" int s2s_upsample2x_fwd_family(int ldx, int ldy, int B, int Hin, int Win, int Hout, int Wout, int C,
+                                         int reference) {
+  if (int rc = upsample2x_fwd_check(ldx, ldy, B, Hin, Win, Hout, Wout, C)) return rc;
+  return upsample2x_fwd_family(ldx, ldy, B, Hin, Win, Wout, C, reference != 0);
 }
 
 namespace {

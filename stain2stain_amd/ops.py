@@ -616,16 +616,28 @@ def bn_relu_bwd(g1: Optional[torch.Tensor], gp: Optional[torch.Tensor], x: torch
 # resampling
 # ------------------------------------------------------------------------------------------------
 @_timed("upsample2x_fwd")
-def upsample2x_fwd(x: torch.Tensor, out: torch.Tensor, bias_nc: Optional[torch.Tensor] = None) -> None:
+def upsample2x_fwd(x: torch.Tensor, out: torch.Tensor, bias_nc: Optional[torch.Tensor] = None,
+                   _reference: bool = False) -> None:
+    """``_reference`` (tests only): the row-sweep kernel that the register-window kernel replaced; same bits."""
     B, Hin, Win, C = x.shape
     _, Hout, Wout, Co = out.shape
     if Co != C or out.dtype != x.dtype:
         raise RuntimeError("stain2stain_amd: upsample output slice mismatch")
     px, ldx = _nhwc(x)
     py, ldy = _nhwc(out)
-    rc = _L().s2s_upsample2x_bilinear_ac_fwd(_dt(x), px, ldx, _f32(bias_nc), py, ldy, B, Hin, Win, Hout, Wout, C,
-                                             _stream())
+    fn = _L().s2s_upsample2x_bilinear_ac_fwd_ref if _reference else _L().s2s_upsample2x_bilinear_ac_fwd
+    rc = fn(_dt(x), px, ldx, _f32(bias_nc), py, ldy, B, Hin, Win, Hout, Wout, C, _stream())
     _native.check(rc, "upsample2x_fwd")
+
+
+def upsample2x_fwd_family(x: torch.Tensor, out: torch.Tensor, _reference: bool = False) -> int:
+    """Which kernel ``upsample2x_fwd`` launches for these tensors (tests): 0 row sweep, 1 the register-window kernel."""
+    B, Hin, Win, C = x.shape
+    _, Hout, Wout, _ = out.shape
+    rc = _L().s2s_upsample2x_fwd_family(_nhwc(x)[1], _nhwc(out)[1], B, Hin, Win, Hout, Wout, C, int(_reference))
+    if rc < 0:
+        _native.check(rc, "upsample2x_fwd_family")
+    return rc
 
 
 @_timed("upsample2x_bwd")
