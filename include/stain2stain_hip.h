@@ -586,6 +586,38 @@ int s2s_register_pick(const long* tsum, const long* sums, const int* center, int
 int s2s_shift_tiles_u8(const void* img, long pitch, long img_stride, int B, int H, int W, int C, const int* shift,
                        int fill, void* out, long out_pitch, long out_img, void* stream);
 
+/* ---- dense region alignment: shift-field cleaning and warp (warp.hip) --------------
+ * Displacements are in 1/16 pixel.  A field is D int [Gy][Gx][2] = (dy, dx); node (gy, gx) is the centre of cell
+ * (gy, gx) of an H x W region, Gy = H / cell, Gx = W / cell.  Dense displacement, per axis in doubled coordinates:
+ * span = 2 cell, u = 2 p + 1 - cell; G >= 2: g0 = clamp(floor(u / span), 0, G - 2), g1 = g0 + 1, w = clamp(u - g0 span,
+ * 0, span); G = 1: g0 = g1 = 0, w = 0 (positions outside the node centres, the ragged remainder included, take the
+ * nearest node's value).  In 64 bits num = (span - wy) ((span - wx) D[y0][x0] + wx D[y0][x1]) + wy ((span - wx) D[y1][x0]
+ * + wx D[y1][x1]); d = floor((num + span^2 / 2) / span^2), clamped to +-16 max_shift per component by the kernel.
+ * Image sampling (C = 3): sy = 16 y + d_y, iy = sy >> 4 (arithmetic), fy = sy & 15, columns alike; taps p00 = T[iy][ix],
+ *   p01 = T[iy][ix + 1], p10 = T[iy + 1][ix], p11 = T[iy + 1][ix + 1]; a tap outside [0, H) x [0, W) of the whole region
+ *   takes fill and is not read; out = ((16 - fy) ((16 - fx) p00 + fx p01) + fy ((16 - fx) p10 + fx p11) + 128) >> 8.
+ *   out[y][x] is the target brought onto src[y][x]: a constant field 16 (dy, dx) is s2s_shift_tiles_u8 byte for byte.
+ * Mask sampling (C = 1): nearest, iy = (sy + 8) >> 4, ix alike, one tap, fill outside.
+ * s2s_warp_region_u8: src = rows [src_row0, src_row0 + src_rows) of the uint8 [H][W][C] region, out = rows [row0, row0 +
+ *   rows) of the result; pitches in bytes, any pitch >= W C and any base alignment; field DEVICE, any values.  Shape
+ *   status when the rows present do not cover [max(0, row0 - max_shift - 1), min(H, row0 + rows + max_shift + 1)), when
+ *   Gy != H / cell, Gx != W / cell, cell < 1 or cell > 2^14 (num must fit 64 bits), Gy Gx outside 1 .. 65536, max_shift
+ *   outside 0 .. 1024, or a pitch is smaller than a row.  One launch; the result does not depend on the banding.
+ * s2s_field_clean: shift DEVICE int [Gy][Gx][2] in pixels, reliable DEVICE uint8 [Gy][Gx]; a cell is reliable when its
+ *   byte is not 0 and max(|dy|, |dx|) <= max_shift.  (1) All cells are judged against the input: a reliable cell with n >= 3
+ *   reliable cells among its 8 neighbours is dropped when max(|dy - med_y|, |dx - med_x|) > max_dev, med the
+ *   component-wise lower median (element (n - 1) / 2 of the sorted values) of those neighbours.  (2) field = 16 shift on
+ *   the kept cells, which are known.  (3) Jacobi iterations on the previous iteration's state: every unknown cell with
+ *   n >= 1 known 8-neighbours becomes floor((2 sum + n) / (2 n)) per component over them and known; until nothing is
+ *   unknown (at most max(Gy, Gx) - 1 iterations).  No cell kept: all zeros, 0 iterations.  field int [Gy][Gx][2] in
+ *   1/16 px; kept uint8 [Gy][Gx] (1 measured, 0 filled); stats int [2] = cells kept, iterations run; work int
+ *   [6 Gy Gx].  Shape status for Gy Gx outside 1 .. 65536, max_shift outside 0 .. 1024, max_dev < 0.  One workgroup. */
+int s2s_field_clean(const int* shift, const void* reliable, int Gy, int Gx, int max_dev, int max_shift, int* field,
+                    void* kept, int* stats, int* work, void* stream);
+int s2s_warp_region_u8(const void* src, long src_pitch, int src_row0, int src_rows, const int* field, int Gy, int Gx,
+                       int cell, int max_shift, int H, int W, int C, int fill, int row0, int rows, void* out,
+                       long out_pitch, void* stream);
+
 /* ---- loss variants and class conditioning (loss_variants.hip) -- SURVEY section 8 row f4 -----------------
  * ROI-weighted MSE (conditional_flow_matching_masked.py:76-90): w = 1 + roi_lambda * mask,
  *   out[0] = sum(w (v-u)^2) / (sum(w) + 1e-8), w broadcast over C.  v, u: float[B][C][HW]; mask: float[B][HW];

@@ -31,6 +31,7 @@ from .augment import (PairedAugmenter, paired_augment, sample_d4_params, sample_
                       stain_jitter_maps)
 from .registration import (overlap_boxes, region_shift_field, register_pairs, registered_quality,
                            sample_crop_params_within, shift_tiles, structure_map, structure_weights)
+from .warp import clean_shift_field, register_region, warp_region
 
 __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeEmbedding", "FlowUNet",
            "ConditionalFlowMatcher", "ConditionalFlowMatchingModule", "MultiTaskFlowMatchingModule", "euler_generate", "dopri5_generate", "euler_integrate", "dopri5_integrate", "SolverConfig", "GraphedVelocity",
@@ -45,4 +46,5 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "label_components", "stain_objects", "stain_object_agreement", "region_stain_objects",
            "paired_augment", "stain_augment", "stain_jitter_maps", "sample_d4_params", "sample_stain_jitter",
            "PairedAugmenter", "structure_weights", "structure_map", "register_pairs", "shift_tiles", "overlap_boxes",
-           "sample_crop_params_within", "registered_quality", "region_shift_field"]
+           "sample_crop_params_within", "registered_quality", "region_shift_field",
+           "clean_shift_field", "warp_region", "register_region"]
