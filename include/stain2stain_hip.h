@@ -618,6 +618,34 @@ int s2s_warp_region_u8(const void* src, long src_pitch, int src_row0, int src_ro
                        int cell, int max_shift, int H, int W, int C, int fill, int row0, int rows, void* out,
                        long out_pitch, void* stream);
 
+/* ---- tile quality control: focus, ink and dark-artefact counts (qc.hip) -----------
+ * Integer throughout.  mx / mn = max / min(R, G, B); tissue = mn < white and mx >= black; Y = (77 R + 150 G + 29 B + 128)
+ * >> 8; L(y, x) = Y(y-1, x) + Y(y+1, x) + Y(y, x-1) + Y(y, x+1) - 4 Y(y, x); a focus pixel is a tissue pixel with
+ * 1 <= y <= H - 2 and 1 <= x <= W - 2 of the IMAGE (its neighbours may lie outside the window); green = tissue and
+ * G - max(R, B) >= ink_chroma; blue = tissue and B - R >= ink_chroma and G >= R; dark = tissue and mx < dark.
+ * A window is the win_h x win_w rectangle at origins[w] = (top, left), clipped to the image on all four sides; an owner
+ * is window w of sample b, owner index b n + w.  Per owner eight int64 numbers: tissue, focus pixels, sum L, sum L^2
+ * (over focus pixels), sum Y over tissue, green, blue, dark.
+ * s2s_qc_chunks: chunks per window (16 rows x 256 columns each); a slab is long [B n chunks][8].  Shape status for
+ *   sizes outside 1 .. 2^30.
+ * s2s_qc_windows_u8: img = rows [band_top, band_top + band_h) of the uint8 [H][W][3] image, per sample at img_stride
+ *   bytes, any pitch >= 3 W and any base alignment; origins DEVICE int [n][2], any values.  The launch accounts for image
+ *   rows [row0, row1) of every window and writes its WHOLE slab (zeros for a chunk with no row in range).  Shape status
+ *   when the rows present do not cover [max(0, row0 - 1), min(H, row1 + 1)), for white outside 1 .. 256, black outside
+ *   0 .. 255, ink_chroma outside 1 .. 255, dark outside 0 .. 256, B outside 1 .. 65535, n chunks > 2^32.  One launch.
+ * s2s_qc_finalize: counts long [owners][8] = (accumulate ? counts : 0) + the sum of the owner's nchunk chunks; launches
+ *   over disjoint row ranges that together cover the image add up to the exact counts in any order.  derived double
+ *   [owners][5], from the counts as they then stand, every operation rounded on its own and 0 where the denominator is
+ *   0: focus = lap_sq / focus_n - (lap_sum / focus_n)^2, tissue / area (the window's pixels inside the image, from
+ *   origins [n][2] and the sizes, owners a multiple of n), (green + blue) / tissue, dark / tissue, luma_sum / tissue.
+ *   One launch. */
+int s2s_qc_chunks(int win_h, int win_w);
+int s2s_qc_windows_u8(const void* img, long pitch, long img_stride, int B, int band_top, int band_h, int H, int W,
+                      const int* origins, int n, int win_h, int win_w, int row0, int row1, int white, int black,
+                      int ink_chroma, int dark, long* slab, void* stream);
+int s2s_qc_finalize(const long* slab, long owners, int nchunk, int accumulate, const int* origins, int n, int H, int W,
+                    int win_h, int win_w, long* counts, double* derived, void* stream);
+
 /* ---- loss variants and class conditioning (loss_variants.hip) -- SURVEY section 8 row f4 -----------------
  * ROI-weighted MSE (conditional_flow_matching_masked.py:76-90): w = 1 + roi_lambda * mask,
  *   out[0] = sum(w (v-u)^2) / (sum(w) + 1e-8), w broadcast over C.  v, u: float[B][C][HW]; mask: float[B][HW];

@@ -32,6 +32,7 @@ from .augment import (PairedAugmenter, paired_augment, sample_d4_params, sample_
 from .registration import (overlap_boxes, region_shift_field, register_pairs, registered_quality,
                            sample_crop_params_within, shift_tiles, structure_map, structure_weights)
 from .warp import clean_shift_field, register_region, warp_region
+from .qc import qc_keep, region_qc, region_qc_map, tile_qc, window_sums
 
 __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeEmbedding", "FlowUNet",
            "ConditionalFlowMatcher", "ConditionalFlowMatchingModule", "MultiTaskFlowMatchingModule", "euler_generate", "dopri5_generate", "euler_integrate", "dopri5_integrate", "SolverConfig", "GraphedVelocity",
@@ -47,4 +48,5 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "paired_augment", "stain_augment", "stain_jitter_maps", "sample_d4_params", "sample_stain_jitter",
            "PairedAugmenter", "structure_weights", "structure_map", "register_pairs", "shift_tiles", "overlap_boxes",
            "sample_crop_params_within", "registered_quality", "region_shift_field",
-           "clean_shift_field", "warp_region", "register_region"]
+           "clean_shift_field", "warp_region", "register_region",
+           "tile_qc", "region_qc", "region_qc_map", "qc_keep", "window_sums"]
