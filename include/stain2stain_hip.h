@@ -534,6 +534,44 @@ int s2s_objects_scores(const int* count_pred, const int* count_target, const int
 int s2s_objects_density(const long* kept_pixels, const long* tissue, const int* count, int B,
                         const double* mm2_per_pixel, float* burden, double* per_mm2, void* stream);
 
+/* ---- mask morphology and boundary metrics: exact distance transform (morphology.hip) -
+ * Masks are bytes [B][H][.] (pitch, img_stride in bytes), foreground iff the byte is not 0.  H, W <= 32767 (so that
+ *   H^2 + W^2 < 2^31) and B <= 65535; anything beyond is refused with the shape status.  Nothing lies outside the
+ *   image.  FAR = 2^31 - 1.  Outputs are dense [B][H][W].  scratch: int32 words, 8-byte aligned.
+ * s2s_morph_words(B, H, W, agreement): the words s2s_morph_edt / s2s_morph_threshold (agreement = 0) or
+ *   s2s_morph_boundary_agreement (agreement = 1) need; s2s_morph_fill_holes_words: those of s2s_morph_fill_holes (the
+ *   labelling's own scratch included).  Negative: a status code.
+ * s2s_morph_edt: out int = the squared distance to the nearest background pixel (to_foreground = 0) or foreground pixel
+ *   (1) of the same sample, FAR when the sample has none; values above max_d2 are reported as FAR (max_d2 = FAR: no
+ *   limit).  Four launches.
+ * s2s_morph_threshold: out bytes = D_fg <= r2 (erode = 0: dilation by the disc of squared radius r2) or D_bg > r2
+ *   (erode = 1), 0 <= r2 < FAR.  The search stops at r2.  Four launches, no int32 map.
+ * s2s_morph_boundary: out bytes = 1 on foreground pixels with a 4-neighbour that is background or outside the image.
+ * s2s_morph_fill_holes: out bytes = mask != 0, or the pixel lies in a connectivity-(4 or 8)-connected component of the
+ *   background that has no pixel on the first or last row or column.
+ * s2s_morph_boundary_agreement: per sample, the pooled squared distances from every boundary pixel of pred to the nearest
+ *   boundary pixel of target and the other way round; leaves max, the percentile-th nearest-rank percentile (1..100),
+ *   the sum of isqrt(65536 s) and #{s <= tol2} in scratch.  s2s_morph_boundary_finalize (same scratch, B, H, W) writes
+ *   max_d2, pq_d2, valid int [B]; sum_q8, within, boundary_pred, boundary_target long [B]; hausdorff = sqrt(max_d2), hd =
+ *   sqrt(pq_d2), assd = sum_q8 / (256 n), surface_dice = within / n double [B], n = boundary_pred + boundary_target.
+ *   Both boundaries empty: integers 0, surface_dice 1, valid 0.  One empty: max_d2 = pq_d2 = (H-1)^2 + (W-1)^2, sum_q8 =
+ *   n isqrt(65536 max_d2), within 0, valid 0.  Fifteen + one launches, no host synchronisation. */
+long s2s_morph_words(int B, int H, int W, int agreement);
+long s2s_morph_fill_holes_words(int B, int H, int W);
+int s2s_morph_edt(const void* mask, long pitch, long img_stride, int B, int H, int W, int to_foreground, int max_d2,
+                  int* scratch, int* out, void* stream);
+int s2s_morph_threshold(const void* mask, long pitch, long img_stride, int B, int H, int W, int erode, int r2,
+                        int* scratch, void* out, void* stream);
+int s2s_morph_boundary(const void* mask, long pitch, long img_stride, int B, int H, int W, void* out, void* stream);
+int s2s_morph_fill_holes(const void* mask, long pitch, long img_stride, int B, int H, int W, int connectivity,
+                         int* scratch, void* out, void* stream);
+int s2s_morph_boundary_agreement(const void* pred, long pred_pitch, long pred_img, const void* target, long target_pitch,
+                                 long target_img, int B, int H, int W, int tol2, int percentile, int* scratch,
+                                 void* stream);
+int s2s_morph_boundary_finalize(const int* scratch, int B, int H, int W, int* max_d2, int* pq_d2, long* sum_q8,
+                                long* within, long* boundary_pred, long* boundary_target, int* valid, double* hausdorff,
+                                double* hd, double* assd, double* surface_dice, void* stream);
+
 /* ---- fused paired augmentation: crop, D4, stain jitter, masks (augment.hip) --------
  * Geometry: params is a DEVICE int [B][param_cols], param_cols 4 or 5 = (top, left, hflip, vflip[, transpose]); with
  *   f[a][b] = img[n][top + (vflip ? S-1-a : a)][left + (hflip ? S-1-b : b)], out[y][x] = transpose ? f[x][y] : f[y][x].

@@ -33,6 +33,7 @@ from .registration import (overlap_boxes, region_shift_field, register_pairs, re
                            sample_crop_params_within, shift_tiles, structure_map, structure_weights)
 from .warp import clean_shift_field, register_region, warp_region
 from .qc import qc_keep, region_qc, region_qc_map, tile_qc, window_sums
+from .morphology import distance_transform, fill_holes, mask_boundary, mask_boundary_agreement, mask_morphology
 
 __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeEmbedding", "FlowUNet",
            "ConditionalFlowMatcher", "ConditionalFlowMatchingModule", "MultiTaskFlowMatchingModule", "euler_generate", "dopri5_generate", "euler_integrate", "dopri5_integrate", "SolverConfig", "GraphedVelocity",
@@ -49,4 +50,5 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "PairedAugmenter", "structure_weights", "structure_map", "register_pairs", "shift_tiles", "overlap_boxes",
            "sample_crop_params_within", "registered_quality", "region_shift_field",
            "clean_shift_field", "warp_region", "register_region",
-           "tile_qc", "region_qc", "region_qc_map", "qc_keep", "window_sums"]
+           "tile_qc", "region_qc", "region_qc_map", "qc_keep", "window_sums",
+           "distance_transform", "mask_morphology", "fill_holes", "mask_boundary", "mask_boundary_agreement"]

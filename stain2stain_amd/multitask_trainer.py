@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
-from . import engine, evaluation, ops
+from . import engine, evaluation, morphology, ops
 from .components import FlowMatchingDecoder, SegmentationDecoder, SharedEncoder
 from .ddp import all_reduce_mean_scalar
 from .ema import TrainerEMA
@@ -226,14 +226,21 @@ class MultiTaskTrainer:
 
     def evaluate(self, source: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, t: Optional[torch.Tensor] = None,
                  accumulator: Optional[evaluation.EvalAccumulator] = None,
-                 use_ema: bool = False) -> Dict[str, torch.Tensor]:
+                 use_ema: bool = False, boundary: Optional[dict] = None) -> Dict[str, torch.Tensor]:
         """The validation / test values of one batch as device scalars: {"loss", "flow_loss", "seg_loss", "seg_dice",
         "seg_bce" | "seg_ce", "dice_coef", "iou"} (the reference's logging suffixes; dice_coef / iou as its test_step
         computes them, per-class means in the multiclass form).  Path sample, eval-mode forward of both heads
         (BatchNorm from the running statistics), forward-only head + MSE, one-pass segmentation loss + metrics.  Touches
         no training state, never waits for the device, runs no collective (``accumulator.compute()`` does, once) and
         uses workspaces of its own.  ``accumulator``: the batch is added to it with weight ``source.shape[0]``.
-        ``use_ema``: score the averaged networks (``ema_model()``; a collective with ``sharded_optimizer``)."""
+        ``use_ema``: score the averaged networks (``ema_model()``; a collective with ``sharded_optimizer``).
+        ``boundary``: arguments of ``mask_boundary_agreement`` (``{}`` for its defaults); the binary head's
+        ``logits > 0`` is scored against ``mask > 0`` and the batch means of hd, assd and surface_dice are added as
+        "boundary/hd", "boundary/assd" and "boundary/surface_dice" (fp64).  Binary form only."""
+        if boundary is not None:
+            if self.num_classes is not None:
+                raise ValueError("MultiTaskTrainer.evaluate: boundary metrics are defined for the binary mask head only")
+            morphology._check_agreement(**{"tolerance": 2, "percentile": 95, **boundary}, what="MultiTaskTrainer.evaluate")
         with ops.workspace_owner(self._eval_owner), evaluation.eval_grad_mode():
             x0, x1 = source.float().contiguous(), target.float().contiguous()
             if t is None:
@@ -249,6 +256,11 @@ class MultiTaskTrainer:
             second = "seg_ce" if self.num_classes is not None else "seg_bce"
             out = {"loss": flow + float(self.seg_loss_weight) * d["seg"], "flow_loss": flow, "seg_loss": d["seg"],
                    "seg_dice": d["seg_dice"], second: d[second], "dice_coef": d["dice_coef"], "iou": d["iou"]}
+            if boundary is not None:
+                B, H, W = logits.shape[0], logits.shape[-2], logits.shape[-1]
+                a = morphology.mask_boundary_agreement((logits > 0).reshape(B, H, W), (mask > 0).reshape(B, H, W),
+                                                       **boundary)
+                out.update({f"boundary/{k}": a[k].mean() for k in ("hd", "assd", "surface_dice")})
         if accumulator is not None:
             accumulator.add(out, x0.shape[0])
         return out
