@@ -86,6 +86,10 @@ int s2s_debug_conv_clock(long* out_host, int n);
  * autograd's conv2d weight gradient for the same layers.  part: float[splits][9][Cout][c0+c1] scratch;
  * grad_oihw: float[Cout][c0+c1][3][3], overwritten or accumulated. */
 int s2s_conv3x3_wgrad_splits(int dtype, int B, int H, int W, int Cin, int Cout);
+/* diagnostic: the launch plan of s2s_conv3x3_wgrad_nhwc for this problem, from the launcher's own host code.
+ * what: 0 = splits, 1 = 8x16 pixel tiles, 2 = XCD-aware workgroup order (0 / 1), 3 = waves per fold group (4 / 16),
+ * 4 = kernel (0 = bf16 DMA, 1 = fp32 register-staged); a negative status for a shape / dtype the launch refuses. */
+int s2s_conv3x3_wgrad_plan(int dtype, int B, int H, int W, int Cin, int Cout, int what);
 int s2s_conv3x3_wgrad_nhwc(int dtype, const void* dy, int lddy, int Cout, const void* x0, int ld0, int c0,
                            const void* x1, int ld1, int c1, float* part, float* grad_oihw, int accumulate,
                            int B, int H, int W, void* stream);
@@ -106,6 +110,10 @@ int s2s_stem_wgrad_blocks(int B, int H, int W);
 /* part: float[ceil(Cin/3)][2*blocks][Cout][32]; dbias may be NULL */
 int s2s_stem_conv3x3_wgrad(int dtype, const void* dy, int lddy, const float* x_nchw, float* part, float* dw_oihw,
                            float* dbias, int accumulate, int B, int H, int W, int Cin, int Cout, void* stream);
+/* diagnostic: the kernels s2s_head_conv1x1_fwd (forward = 1) / _bwd (forward = 0) take, from their own dispatch: 1 ... 64 =
+ * the lane-per-piece form with that many lanes per pixel (C = 8 lanes), 104 / 108 = the one-thread-per-pixel kernels
+ * with 4 / 8 outputs; a negative status for a launch that is refused (Cout > 8; backward: Cout (C + 1) > 2048). */
+int s2s_head_family(int dtype, int B, int H, int W, int C, int Cout, int forward);
 int s2s_head_conv1x1_fwd(int dtype, const void* x, int ldx, const float* w, const float* bias, float* y_nchw, int B,
                          int H, int W, int C, int Cout, void* stream);
 int s2s_head_wgrad_blocks(int B, int H, int W);

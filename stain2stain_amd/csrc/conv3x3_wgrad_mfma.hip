@@ -470,9 +470,7 @@ int launch_wgrad_dma(WgradArgs& a, hipStream_t s) {
   auto kern = conv3x3_wgrad_dma_kernel<TH, TW>;
   static unsigned long long attr_devs = 0;   // hipFuncSetAttribute is per device
   if (int rc = s2s_allow_dyn_lds(reinterpret_cast<const void*>(kern), lds, &attr_devs)) return rc;
-  dim3 grid(cdiv(a.c0 + a.c1, 64), cdiv(a.Cout, 64), a.S);
-  static const int xcd_aware = [] { const char* e = getenv("S2S_WGRAD_XCD"); return e ? atoi(e) : 1; }();
-  a.xcd = xcd_aware && ((long)grid.x * grid.y * grid.z) % 8 == 0;
+  dim3 grid(cdiv(a.c0 + a.c1, 64), cdiv(a.Cout, 64), a.S);   // (a.xcd: set by the caller from conv3x3_wgrad_plan)
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
   S2S_LAUNCH_CHECK();
   return S2S_OK;
@@ -1220,6 +1218,44 @@ extern "C" int s2s_conv3x3_wgrad_splits(int dtype, int B, int H, int W, int Cin,
   return s;
 }
 
+// What a 3x3 weight-gradient launch does, decided in one place: s2s_conv3x3_wgrad_phase launches from this plan and
+// s2s_conv3x3_wgrad_plan reports it.
+namespace {
+struct Wgrad3x3Plan {
+  int splits, tiles;
+  int xcd;      // conv3x3_wgrad_dma_kernel's XCD-aware workgroup order (S2S_WGRAD_XCD, and a grid that divides by 8)
+  int fold;     // waves per fold group of wgrad_reduce_kernel: 16 for a narrow weight with many slabs, else 4
+  int kernel;   // 0 = conv3x3_wgrad_dma_kernel (bf16), 1 = conv3x3_wgrad_kernel<float> (register-staged)
+};
+int conv3x3_wgrad_plan(int dtype, int B, int H, int W, int Cin, int Cout, Wgrad3x3Plan& p) {
+  const int s = s2s_conv3x3_wgrad_splits(dtype, B, H, W, Cin, Cout);
+  if (s < 0) return s;
+  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  p.splits = s;
+  p.tiles = wgrad_ntiles(B, H, W);
+  p.kernel = dtype == S2S_BF16 ? 0 : 1;
+  static const int xcd_aware = [] { const char* e = getenv("S2S_WGRAD_XCD"); return e ? atoi(e) : 1; }();
+  p.xcd = p.kernel == 0 && xcd_aware && ((long)cdiv(Cin, 64) * cdiv(Cout, 64) * s) % 8 == 0;
+  p.fold = ((long)Cout * Cin <= 32768 && s >= 32) ? 16 : 4;
+  return S2S_OK;
+}
+}  // namespace
+
+// what: 0 = splits, 1 = pixel tiles, 2 = XCD-aware workgroup order (0 / 1), 3 = waves per fold group (4 / 16),
+// 4 = kernel (0 = bf16 DMA, 1 = fp32 register-staged)
+extern "C" int s2s_conv3x3_wgrad_plan(int dtype, int B, int H, int W, int Cin, int Cout, int what) {
+  Wgrad3x3Plan p{};
+  if (int rc = conv3x3_wgrad_plan(dtype, B, H, W, Cin, Cout, p)) return rc;
+  switch (what) {
+    case 0: return p.splits;
+    case 1: return p.tiles;
+    case 2: return p.xcd;
+    case 3: return p.fold;
+    case 4: return p.kernel;
+    default: return S2S_ERR_SHAPE;
+  }
+}
+
 // phases: 1 = the split MFMA kernel (partial slabs into `part`), 2 = the fold of the slabs into the OIHW gradient,
 // 3 = both.  Two calls with phases 1 and 2 equal one call with 3; a profiler uses them to time the two kernels apart.
 extern "C" int s2s_conv3x3_wgrad_phase(int dtype, const void* dy, int lddy, int Cout, const void* x0, int ld0, int c0,
@@ -1234,16 +1270,18 @@ extern "C" int s2s_conv3x3_wgrad_phase(int dtype, const void* dy, int lddy, int 
   a.dy = dy; a.x0 = x0; a.x1 = x1; a.part = part;
   a.lddy = lddy; a.Cout = Cout; a.ld0 = ld0; a.c0 = c0; a.ld1 = ld1; a.c1 = c1;
   a.B = B; a.H = H; a.W = W; a.lgc = 0; a.lgh = a.lgw = 0;
-  a.S = s2s_conv3x3_wgrad_splits(dtype, B, H, W, c0 + c1, Cout);
+  Wgrad3x3Plan plan{};
+  if (int prc = conv3x3_wgrad_plan(dtype, B, H, W, c0 + c1, Cout, plan)) return prc;
+  a.S = plan.splits;
+  a.xcd = plan.xcd;
   hipStream_t s = static_cast<hipStream_t>(stream);
   int rc = S2S_OK;
-  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
-  if (!(phases & 1)) { if (a.S > wgrad_ntiles(B, H, W)) return S2S_ERR_SHAPE; }
-  else if (dtype == S2S_BF16) rc = launch_wgrad_dma<8, 16>(a, s);
+  if (!(phases & 1)) { if (a.S > plan.tiles) return S2S_ERR_SHAPE; }
+  else if (plan.kernel == 0) rc = launch_wgrad_dma<8, 16>(a, s);
   else rc = launch_wgrad<float, 8, 16>(a, s);
   if (rc != S2S_OK || !(phases & 2)) return rc;
   const long n = (long)Cout * (c0 + c1);
-  if (n <= 32768 && a.S >= 32)
+  if (plan.fold == 16)
     hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3((unsigned)((n + 63) / 64)), dim3(1024), 0, s, part, grad_oihw,
                        a.S, Cout, c0 + c1, accumulate);
   else

@@ -661,18 +661,31 @@ __global__ __launch_bounds__(256) void head_lanes_kernel(const T* __restrict__ x
   }
 }
 
-// launch head_lanes_kernel for C = 8 PCB (PCB a power of two <= 64) and Cout <= 4; false when the shape is not taken
+// Which kernels a head launch takes (s2s_head_family): the lane-per-piece form returns its PCB (C = 8 PCB, PCB a power of
+// two <= 64, Cout <= 4), the one-thread-per-pixel kernels HEAD_FALLBACK + MO (MO = 4 or 8 outputs unrolled); a negative
+// status is a launch the entry points refuse.  s2s_head_conv1x1_fwd / _bwd dispatch on this value and on nothing else.
+constexpr int HEAD_FALLBACK = 100;
+int head_family(int dtype, int B, int H, int W, int C, int Cout, int forward) {
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 8) || Cout <= 0 || Cout > HEAD_WIDE_COUT) return S2S_ERR_SHAPE;
+  if (!forward && Cout * (C + 1) > 2048) return S2S_ERR_SHAPE;     // head_wgrad_kernel: 8 outputs a thread
+  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  const long npix = (long)B * H * W;
+  const int pcb = C / 8;
+  if (Cout <= HEAD_MAX_COUT && npix < (1L << 31) - (1L << 20) && pcb <= 64 && !(pcb & (pcb - 1))) return pcb;
+  return HEAD_FALLBACK + (Cout <= 4 ? 4 : 8);
+}
+
+// launch head_lanes_kernel<T, PP, FWD> for the PP head_family chose
 template <typename T, bool FWD>
-bool launch_head_lanes(const void* x, int ldx, const float* w, const float* bias, const float* dy, float* v, void* dx,
-                       int lddx, float* part, int nb, long npix, int HW, int C, int Cout, hipStream_t s) {
-  if (Cout > HEAD_MAX_COUT || (C % 8) || npix >= (1L << 31) - (1L << 20)) return false;
+void launch_head_lanes(int pp, const void* x, int ldx, const float* w, const float* bias, const float* dy, float* v, void* dx,
+                       int lddx, float* part, int nb, long npix, int HW, int Cout, hipStream_t s) {
 #define S2S_HLN(PP)                                                                                                  \
   hipLaunchKernelGGL((head_lanes_kernel<T, PP, FWD>), dim3(nb), dim3(256), 0, s, (const T*)x, ldx, w, bias, dy, v,   \
                      (T*)dx, lddx, part, npix, HW, Cout);                                                            \
-  return true;
-  switch (C / 8) {
+  break;
+  switch (pp) {
     case 1: S2S_HLN(1) case 2: S2S_HLN(2) case 4: S2S_HLN(4) case 8: S2S_HLN(8) case 16: S2S_HLN(16) case 32: S2S_HLN(32)
-    case 64: S2S_HLN(64) default: return false;
+    case 64: S2S_HLN(64)
   }
 #undef S2S_HLN
 }
@@ -968,29 +981,35 @@ extern "C" int s2s_stem_conv3x3_wgrad(int dtype, const void* dy, int lddy, const
   return S2S_OK;
 }
 
+extern "C" int s2s_head_family(int dtype, int B, int H, int W, int C, int Cout, int forward) {
+  return head_family(dtype, B, H, W, C, Cout, forward);
+}
+
 extern "C" int s2s_head_conv1x1_fwd(int dtype, const void* x, int ldx, const float* w, const float* bias,
                                     float* y_nchw, int B, int H, int W, int C, int Cout, void* stream) {
   if (!x || !w || !y_nchw) return S2S_ERR_NULL;
-  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 8) || (ldx % 8) || Cout <= 0 || Cout > HEAD_WIDE_COUT)
-    return S2S_ERR_SHAPE;
+  if (ldx % 8) return S2S_ERR_SHAPE;
+  const int fam = head_family(dtype, B, H, W, C, Cout, 1);
+  if (fam < 0) return fam;
   const long npix = (long)B * H * W;
   long grid = (npix + 255) / 256;
   if (grid > 4096) grid = 4096;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
-  {
+  if (fam < HEAD_FALLBACK) {
     const int nbl = (int)(((npix + 255) / 256) < 2048 ? ((npix + 255) / 256) : 2048);
-    const bool done = dtype == S2S_BF16
-        ? launch_head_lanes<bf16_t, true>(x, ldx, w, bias, nullptr, y_nchw, nullptr, 8, nullptr, nbl, npix, H * W, C, Cout, s)
-        : launch_head_lanes<float, true>(x, ldx, w, bias, nullptr, y_nchw, nullptr, 8, nullptr, nbl, npix, H * W, C, Cout, s);
-    if (done) { S2S_LAUNCH_CHECK(); return S2S_OK; }
+    if (dtype == S2S_BF16)
+      launch_head_lanes<bf16_t, true>(fam, x, ldx, w, bias, nullptr, y_nchw, nullptr, 8, nullptr, nbl, npix, H * W, Cout, s);
+    else
+      launch_head_lanes<float, true>(fam, x, ldx, w, bias, nullptr, y_nchw, nullptr, 8, nullptr, nbl, npix, H * W, Cout, s);
+    S2S_LAUNCH_CHECK();
+    return S2S_OK;
   }
+  const int mo = fam - HEAD_FALLBACK;
 #define S2S_HEAD_FWD(TT, MO)                                                                                        \
   hipLaunchKernelGGL((head_fwd_kernel<TT, MO>), dim3((int)grid), dim3(256), Cout * C * 4, s, (const TT*)x, ldx, w, \
                      bias, y_nchw, npix, H * W, C, Cout)
-  if (dtype == S2S_BF16) { if (Cout <= 4) S2S_HEAD_FWD(bf16_t, 4); else S2S_HEAD_FWD(bf16_t, 8); }
-  else if (dtype == S2S_F32) { if (Cout <= 4) S2S_HEAD_FWD(float, 4); else S2S_HEAD_FWD(float, 8); }
-  else return S2S_ERR_DTYPE;
+  if (dtype == S2S_BF16) { if (mo == 4) S2S_HEAD_FWD(bf16_t, 4); else S2S_HEAD_FWD(bf16_t, 8); }
+  else { if (mo == 4) S2S_HEAD_FWD(float, 4); else S2S_HEAD_FWD(float, 8); }
 #undef S2S_HEAD_FWD
   S2S_LAUNCH_CHECK();
   return S2S_OK;
@@ -1007,38 +1026,32 @@ extern "C" int s2s_head_conv1x1_bwd(int dtype, const float* dy_nchw, const void*
                                     int lddx, float* part, float* dw, float* dbias, int accumulate, int B, int H, int W,
                                     int C, int Cout, void* stream) {
   if (!dy_nchw || !x || !w || !dx || !part || !dw) return S2S_ERR_NULL;
-  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 8) || (ldx % 8) || (lddx % 8) || Cout <= 0 || Cout > HEAD_WIDE_COUT)
-    return S2S_ERR_SHAPE;
-  if (Cout * (C + 1) > 2048) return S2S_ERR_SHAPE;
+  if ((ldx % 8) || (lddx % 8)) return S2S_ERR_SHAPE;
+  const int fam = head_family(dtype, B, H, W, C, Cout, 0);
+  if (fam < 0) return fam;
   const long npix = (long)B * H * W;
   long grid = (npix + 255) / 256;
   if (grid > 4096) grid = 4096;
   const int nb = s2s_head_wgrad_blocks(B, H, W);
-  const int mo = Cout <= 4 ? 4 : 8;
-  const int lds = (64 * (C + 1) + 64 * mo) * 4;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
-  {
+  if (fam < HEAD_FALLBACK) {
     // one pass over the activation for both gradients (lane-per-piece form, partial dW | db rows per workgroup)
-    const bool done = dtype == S2S_BF16
-        ? launch_head_lanes<bf16_t, false>(x, ldx, w, nullptr, dy_nchw, nullptr, dx, lddx, part, nb, npix, H * W, C, Cout, s)
-        : launch_head_lanes<float, false>(x, ldx, w, nullptr, dy_nchw, nullptr, dx, lddx, part, nb, npix, H * W, C, Cout, s);
-    if (done) {
-      hipLaunchKernelGGL(head_wgrad_reduce_kernel, dim3(cdiv(Cout * (C + 1), 8)), dim3(256), 0, s, part, nb, Cout, C,
-                         dw, dbias, accumulate);
-      S2S_LAUNCH_CHECK();
-      return S2S_OK;
-    }
-  }
+    if (dtype == S2S_BF16)
+      launch_head_lanes<bf16_t, false>(fam, x, ldx, w, nullptr, dy_nchw, nullptr, dx, lddx, part, nb, npix, H * W, Cout, s);
+    else
+      launch_head_lanes<float, false>(fam, x, ldx, w, nullptr, dy_nchw, nullptr, dx, lddx, part, nb, npix, H * W, Cout, s);
+  } else {
+    const int mo = fam - HEAD_FALLBACK;
+    const int lds = (64 * (C + 1) + 64 * mo) * 4;
 #define S2S_HEAD_BWD(TT, MO)                                                                                       \
   hipLaunchKernelGGL((head_bwd_data_kernel<TT, MO>), dim3((int)grid), dim3(256), Cout * C * 4, s, dy_nchw, w,      \
                      (TT*)dx, lddx, npix, H * W, C, Cout);                                                         \
   hipLaunchKernelGGL((head_wgrad_kernel<TT, MO>), dim3(nb), dim3(256), lds, s, dy_nchw, (const TT*)x, ldx, part,   \
                      npix, H * W, C, Cout);
-  if (dtype == S2S_BF16) { if (mo == 4) { S2S_HEAD_BWD(bf16_t, 4) } else { S2S_HEAD_BWD(bf16_t, 8) } }
-  else if (dtype == S2S_F32) { if (mo == 4) { S2S_HEAD_BWD(float, 4) } else { S2S_HEAD_BWD(float, 8) } }
-  else return S2S_ERR_DTYPE;
+    if (dtype == S2S_BF16) { if (mo == 4) { S2S_HEAD_BWD(bf16_t, 4) } else { S2S_HEAD_BWD(bf16_t, 8) } }
+    else { if (mo == 4) { S2S_HEAD_BWD(float, 4) } else { S2S_HEAD_BWD(float, 8) } }
 #undef S2S_HEAD_BWD
+  }
   hipLaunchKernelGGL(head_wgrad_reduce_kernel, dim3(cdiv(Cout * (C + 1), 8)), dim3(256), 0, s, part, nb, Cout, C,
                      dw, dbias, accumulate);
   S2S_LAUNCH_CHECK();

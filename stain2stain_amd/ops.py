@@ -377,6 +377,26 @@ def conv3x3_wgrad(dy: torch.Tensor, x0: torch.Tensor, x1: Optional[torch.Tensor]
     _native.check(rc, "conv3x3_wgrad")
 
 
+def conv3x3_wgrad_plan(dtype: torch.dtype, B: int, H: int, W: int, cin: int, cout: int) -> dict:
+    """What conv3x3_wgrad launches for this problem (s2s_conv3x3_wgrad_plan): splits, 8x16 pixel tiles, XCD-aware order,
+    waves per fold group and the kernel (0 = bf16 DMA, 1 = fp32 register-staged).  Host code only; needs no GPU."""
+    dt = BF16 if dtype == torch.bfloat16 else F32
+    plan = {}
+    for what, name in enumerate(("splits", "tiles", "xcd", "fold", "kernel")):
+        plan[name] = _L().s2s_conv3x3_wgrad_plan(dt, B, H, W, cin, cout, what)
+        _native.check(min(plan[name], 0), "conv3x3_wgrad_plan")
+    return plan
+
+
+HEAD_FALLBACK_MO4, HEAD_FALLBACK_MO8 = 104, 108
+
+
+def head_family(dtype: torch.dtype, B: int, H: int, W: int, C: int, cout: int, forward: bool) -> int:
+    """The kernels head_fwd / head_bwd take (s2s_head_family): 1 ... 64 = lanes per pixel of the lane-per-piece form,
+    HEAD_FALLBACK_MO4 / _MO8 = the one-thread-per-pixel kernels; negative = the launch is refused.  Needs no GPU."""
+    return _L().s2s_head_family(BF16 if dtype == torch.bfloat16 else F32, B, H, W, C, cout, int(forward))
+
+
 @_timed("stem_fwd")
 def stem_fwd(x_nchw: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], dtype: torch.dtype,
              want_stats: bool = True):
@@ -421,14 +441,19 @@ def head_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) -> 
 
 @_timed("head_bwd")
 def head_bwd(dy_nchw: torch.Tensor, x: torch.Tensor, w: torch.Tensor, dw: torch.Tensor, dbias: Optional[torch.Tensor],
-             accumulate: bool = False) -> torch.Tensor:
+             accumulate: bool = False, dx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``dx``: an NHWC view to write the data gradient into (a channel slice of a wider buffer is fine)."""
     B, H, W, C = x.shape
     cout = w.shape[0]
     px, ldx = _nhwc(x)
-    dx = torch.empty((B, H, W, C), dtype=x.dtype, device=x.device)
+    if dx is None:
+        dx = torch.empty((B, H, W, C), dtype=x.dtype, device=x.device)
+    elif dx.dtype != x.dtype or dx.shape != x.shape:
+        raise RuntimeError("stain2stain_amd: head_bwd dx buffer mismatch")
+    pdx, lddx = _nhwc(dx)
     nb = _L().s2s_head_wgrad_blocks(B, H, W)
     part = torch.empty((nb, cout, C + 1), dtype=torch.float32, device=x.device)
-    rc = _L().s2s_head_conv1x1_bwd(_dt(x), _f32(dy_nchw), px, ldx, _f32(w.reshape(cout, C)), dx.data_ptr(), C,
+    rc = _L().s2s_head_conv1x1_bwd(_dt(x), _f32(dy_nchw), px, ldx, _f32(w.reshape(cout, C)), pdx, lddx,
                                    _f32(part), _f32(dw.reshape(cout, C)), _f32(dbias), int(accumulate), B, H, W, C,
                                    cout, _stream())
     _native.check(rc, "head_conv1x1_bwd")

@@ -27,6 +27,7 @@ def test_conv_parity_under_switch(env):
     out = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-p", "no:cacheprovider",
                           os.path.join(ROOT, "tests", "test_ops_gpu.py"), os.path.join(ROOT, "tests", "test_fuzz_gpu.py"),
                           os.path.join(ROOT, "tests", "test_unwritten_memory_gpu.py"),
+                          os.path.join(ROOT, "tests", "test_wgrad_forms_gpu.py"),
                           "-k", "conv3x3 or random_shapes"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env={**os.environ, **env})
     assert out.returncode == 0, out.stdout[-2500:] + out.stderr[-1500:]
