@@ -110,6 +110,12 @@ int s2s_stem_wgrad_blocks(int B, int H, int W);
 /* part: float[ceil(Cin/3)][2*blocks][Cout][32]; dbias may be NULL */
 int s2s_stem_conv3x3_wgrad(int dtype, const void* dy, int lddy, const float* x_nchw, float* part, float* dw_oihw,
                            float* dbias, int accumulate, int B, int H, int W, int Cin, int Cout, void* stream);
+/* test-facing: the kernel that the pipelined bf16 kernel replaced (fp32: the same launch); same arguments, same bits */
+int s2s_stem_conv3x3_wgrad_ref(int dtype, const void* dy, int lddy, const float* x_nchw, float* part, float* dw_oihw,
+                               float* dbias, int accumulate, int B, int H, int W, int Cin, int Cout, void* stream);
+/* test-facing, no launch: which kernel the launch takes (0 the reference kernel, 1 the pipelined one: LDS-DMA for dY,
+ * double-buffered; < 0 the launch's error); reference != 0: as the _ref entry point chooses */
+int s2s_stem_wgrad_family(int dtype, int lddy, int B, int H, int W, int Cin, int Cout, int reference);
 /* diagnostic: the kernels s2s_head_conv1x1_fwd (forward = 1) / _bwd (forward = 0) take, from their own dispatch: 1 ... 64 =
  * the lane-per-piece form with that many lanes per pixel (C = 8 lanes), 104 / 108 = the one-thread-per-pixel kernels
  * with 4 / 8 outputs; a negative status for a launch that is refused (Cout > 8; backward: Cout (C + 1) > 2048). */
@@ -194,6 +200,12 @@ int s2s_bn_relu_bwd_phase(int dtype, const void* g1, int ldg1, const void* gp, i
  * to the input first: x = bottleneck + t[:, :, None, None] (task_decoders.py:119-125). */
 int s2s_upsample2x_bilinear_ac_fwd(int dtype, const void* x, int ldx, const float* bias_nc, void* y, int ldy, int B,
                                    int Hin, int Win, int Hout, int Wout, int C, void* stream);
+/* the up-sampling of relu(bn(x)) straight from the convolution's raw output x (scale / shift: float[C], rows 2 and 3 of
+ * s2s_bn_finalize_b): s2s_bn_relu_apply followed by the entry point above, bit for bit, without the activation in
+ * between.  Register-window shapes only (s2s_upsample2x_fwd_family == 1); others return the shape error. */
+int s2s_upsample2x_bn_relu_fwd(int dtype, const void* x, int ldx, const float* scale, const float* shift,
+                               const float* bias_nc, void* y, int ldy, int B, int Hin, int Win, int Hout, int Wout, int C,
+                               void* stream);
 /* test-facing: the row-sweep kernel that the production forward replaced; same arguments, same bits */
 int s2s_upsample2x_bilinear_ac_fwd_ref(int dtype, const void* x, int ldx, const float* bias_nc, void* y, int ldy, int B,
                                        int Hin, int Win, int Hout, int Wout, int C, void* stream);

@@ -155,6 +155,161 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const T* __restrict__ d
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// bf16: the same computation with its operands in flight while the MFMAs run.  Per tile the kernel above runs global
+// loads -> ds_write -> barrier -> im2col build -> barrier -> 8 MFMA steps -> barrier, with nothing outstanding during the
+// MFMAs; a workgroup walks 8 tiles of the 256^2 x 16 batch that way at 2.0 TB/s.  Here
+//   * the two [pixel][32 co] images of dY arrive by LDS-DMA (global_load_lds_dwordx4, one 16-pixel row of an image per
+//     wave instruction, as conv3x3_wgrad_dma_kernel stages its operands) into the OTHER of two buffers while the
+//     current tile's MFMAs run; pixels past the image and channels past Cout fetch a zero page, so every wave issues the
+//     same 8 DMAs per tile;
+//   * the 27 fp32 taps of a thread's own pixel for the next tile are loaded (predicated) into registers at the same
+//     time, straight from the image -- neighbouring threads' taps overlap, the loads hit in L1 / L2 -- so there is no
+//     fp32 halo in LDS and no barrier between it and the im2col build;
+//   * LDS is two dY buffers of 32 KB and ONE 16 KB patch: 80 KB, two workgroups per CU.  The single patch costs a
+//     second barrier per tile (all MFMAs of tile i before the patch of tile i + 1 is written), with the DMAs still in
+//     flight across it.
+// The arithmetic is the kernel's above: the same tiles in the same order per (block, pixel half) slab, the same chain of
+// eight MFMAs per tile (ks ascending) on the same bf16 values (dY as stored, the patch rounded from the same fp32 taps),
+// the same partial layout: the results are equal bit for bit.
+// ---------------------------------------------------------------------------------------------
+__device__ __attribute__((aligned(64))) char g_stem_zero_page[64];
+
+// LDS-DMA from inline asm (see dma16_asm in conv3x3_wgrad_mfma.hip: the compiler's waitcnt pass does not see it, so
+// completion is tracked by the explicit vmcnt(0) below; M0 carries the wave-uniform LDS destination and is restored)
+__device__ __forceinline__ void stem_dma16(const void* gsrc, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+}
+
+constexpr int STEM_PIPE_LDS = 2 * (2 * 256 * 64) + 256 * 64;      // 81920
+
+__global__ __launch_bounds__(256, 2) void stem_wgrad_pipe_kernel(const bf16_t* __restrict__ dy, int lddy,
+                                                                 const float* __restrict__ x, float* __restrict__ part,
+                                                                 int B, int H, int W, int Cin, int Cout, int tilesY,
+                                                                 int tilesX) {
+  constexpr int NPX = 256;
+  constexpr int DY_IMG = 2 * NPX * 64;      // one buffer: two 32-channel images of 64-B rows
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const ldsP = smem + 2 * DY_IMG;                      // [256][64B]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wco = wave & 1, whalf = wave >> 1;
+  const int co0 = blockIdx.y * 64;
+  const int c0 = blockIdx.z * 3;
+  const int nc = (Cin - c0) < 3 ? (Cin - c0) : 3, K = nc * 9;
+  const int g = lane >> 4, q = (lane & 15) >> 2, pq = lane & 3;
+  const int frag_off = ((g >> 1) * 8 + q) * 64 + ((g & 1) * 16 + pq * 4) * 2;
+  const int ntiles = B * tilesY * tilesX;
+  const int drow = lane >> 2, dslot = lane & 3;              // a DMA lane's pixel of the 16-pixel row, its 8-channel piece
+  const int py = tid >> 4, px = tid & 15;                    // the pixel whose im2col row this thread builds
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+
+  // tile -> (sample, first row, first column)
+  auto origin = [&](int tile, int& n, int& y0, int& x0) {
+    int bt = tile;
+    const int tx = bt % tilesX; bt /= tilesX;
+    const int ty = bt % tilesY;
+    n = bt / tilesY; y0 = ty * 16; x0 = tx * 16;
+  };
+  // DMA group grp = wave + 4 j: image grp / 16 (channels co0 + 32 (grp / 16) ..), tile row grp % 16
+  auto dma_tile = [&](int tile, int buf) {
+    int n, y0, x0;
+    origin(tile, n, y0, x0);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int grp = wave + 4 * j;
+      const int gy = y0 + (grp & 15), gx = x0 + drow, co = co0 + (grp >> 4) * 32 + dslot * 8;
+      const bool in = gy < H && gx < W && co < Cout;
+      const bf16_t* const pix = dy + (((long)n * H + min(gy, H - 1)) * W + min(gx, W - 1)) * lddy + min(co, Cout - 8);
+      const void* const src = in ? (const void*)pix : (const void*)g_stem_zero_page;
+      stem_dma16(src, __builtin_amdgcn_readfirstlane(lds0 + buf * DY_IMG + grp * 1024));
+    }
+  };
+  // the thread's 27 taps (k = ci * 9 + tap) as loaded, bit kk of `in` = tap kk is inside the image and the group's
+  // channels (build_patch zeroes the others: a use of the loaded values here would wait for them in front of the MFMAs),
+  // and its bias column
+  auto load_taps = [&](int tile, float (&tp)[27], unsigned& in, float& one) {
+    int n, y0, x0;
+    origin(tile, n, y0, x0);
+    one = (y0 + py < H && x0 + px < W) ? 1.f : 0.f;          // dY is zero outside anyway
+    // every load is unconditional, from the address clamped into the image and the group's channels: a branch per tap
+    // otherwise
+    in = 0u;
+#pragma unroll
+    for (int kk = 0; kk < 27; ++kk) {
+      const int ci = kk / 9, t = kk - ci * 9;
+      const int gy = y0 + py + t / 3 - 1, gx = x0 + px + t % 3 - 1;
+      in |= (unsigned)(kk < K && gy >= 0 && gy < H && gx >= 0 && gx < W) << kk;
+      const int cc = c0 + min(ci, nc - 1), yy = min(max(gy, 0), H - 1), xx = min(max(gx, 0), W - 1);
+      tp[kk] = x[(((long)n * Cin + cc) * H + yy) * W + xx];
+    }
+  };
+  auto build_patch = [&](const float (&tp)[27], unsigned in, float one) {
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) {
+      float v8[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int kk = c4 * 8 + k;
+        float v = (kk < 27 && ((in >> (kk & 31)) & 1u)) ? tp[kk < 27 ? kk : 0] : 0.f;
+        if (kk == K && c0 == 0) v = one;
+        v8[k] = v;
+      }
+      split_store<1>(ldsP, 0, tid * 64 + c4 * 16, v8);
+    }
+  };
+
+  f32x16 acc;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+  float tp[27], one;
+  unsigned tin;
+  int tile = blockIdx.x, buf = 0;
+  if (tile < ntiles) {
+    dma_tile(tile, 0);
+    load_taps(tile, tp, tin, one);
+    build_patch(tp, tin, one);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (; tile < ntiles; tile += gridDim.x, buf ^= 1) {
+    const bool more = tile + (int)gridDim.x < ntiles;        // block-uniform
+    // Both land while the MFMAs below run.  The taps go first: the compiler cannot see the vmcnt(0) at the loop's end, so
+    // it waits for the previous iteration's tap loads before it overwrites their registers -- a wait that is free as
+    // long as no DMA has been issued yet, and one for the DMAs otherwise.
+    if (more) {
+      load_taps(tile + gridDim.x, tp, tin, one);
+      dma_tile(tile + gridDim.x, buf ^ 1);
+    }
+    __builtin_amdgcn_sched_barrier(0);                       // nothing that waits for those loads moves up here
+    const char* A0 = smem + buf * DY_IMG + wco * (NPX * 64) + frag_off;
+    const char* B0 = ldsP + frag_off;
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+      const int m0 = (whalf * 8 + ks) * 16;
+      const bf16x8 ah = tr_frag8(A0 + m0 * 64);
+      const bf16x8 bh = tr_frag8(B0 + m0 * 64);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (more) {
+      __syncthreads();   // every wave has read the patch of this tile
+      build_patch(tp, tin, one);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the next tile's dY images have landed
+      __syncthreads();
+    }
+  }
+  const int kcol = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int co = co0 + wco * 32 + (j & 3) + 8 * (j >> 2) + 4 * h;
+    if (co < Cout)
+      part[((((long)blockIdx.z * gridDim.x + blockIdx.x) * 2 + whalf) * Cout + co) * 32 + kcol] = acc[j];
+  }
+}
+
 // one workgroup per (output channel, channel group): 32 k-columns x 32 slab groups (1024 slabs: 32 loads a thread)
 __global__ __launch_bounds__(1024) void stem_wgrad_reduce_kernel(const float* part, int nslab, int Cout, int Cin, float* dw, float* db,
                                          int accumulate) {
@@ -954,31 +1109,72 @@ extern "C" int s2s_stem_wgrad_blocks(int B, int H, int W) {
   return nt < cap ? nt : cap;
 }
 
-// part: float[ceil(Cin/3)][2*blocks][Cout][32]
-extern "C" int s2s_stem_conv3x3_wgrad(int dtype, const void* dy, int lddy, const float* x_nchw, float* part,
-                                      float* dw_oihw, float* dbias, int accumulate, int B, int H, int W, int Cin,
-                                      int Cout, void* stream) {
-  if (!dy || !x_nchw || !part || !dw_oihw) return S2S_ERR_NULL;
+namespace {
+
+// Which kernel a stem weight-gradient launch takes (s2s_stem_wgrad_family hands it to tests): bf16 the pipelined kernel,
+// fp32 (three images per operand: 240 KB of LDS in that form) and `reference` the kernel it replaced
+enum StemWgradFamily { kStemWgradReference = 0, kStemWgradPipelined = 1 };
+
+int stem_wgrad_family(int dtype, bool reference) { return dtype == S2S_BF16 && !reference ? kStemWgradPipelined : kStemWgradReference; }
+
+int stem_wgrad_check(int dtype, int B, int H, int W, int Cin, int Cout, int lddy) {
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin > 6 || Cout <= 0 || (Cout % 8) || (lddy % 8))
     return S2S_ERR_SHAPE;
+  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  return S2S_OK;
+}
+
+// part: float[ceil(Cin/3)][2*blocks][Cout][32]
+int stem_wgrad_launch(int dtype, const void* dy, int lddy, const float* x_nchw, float* part, float* dw_oihw, float* dbias,
+                      int accumulate, int B, int H, int W, int Cin, int Cout, void* stream, bool reference) {
+  if (!dy || !x_nchw || !part || !dw_oihw) return S2S_ERR_NULL;
+  if (int rc = stem_wgrad_check(dtype, B, H, W, Cin, Cout, lddy)) return rc;
   const int nb = s2s_stem_wgrad_blocks(B, H, W);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(nb, cdiv(Cout, 64), cdiv(Cin, 3));
-  if (dtype == S2S_BF16) {
+  if (stem_wgrad_family(dtype, reference) == kStemWgradPipelined) {
+    if ((uintptr_t)dy & 15) return S2S_ERR_ALIGN;          // the DMA moves whole 16-byte pieces
+    static unsigned long long attr_devs = 0;   // hipFuncSetAttribute is per device
+    if (int rc = s2s_allow_dyn_lds(reinterpret_cast<const void*>(stem_wgrad_pipe_kernel), STEM_PIPE_LDS, &attr_devs)) return rc;
+    hipLaunchKernelGGL(stem_wgrad_pipe_kernel, grid, dim3(256), STEM_PIPE_LDS, s, (const bf16_t*)dy, lddy, x_nchw, part, B,
+                       H, W, Cin, Cout, cdiv(H, 16), cdiv(W, 16));
+  } else if (dtype == S2S_BF16) {
     const int lds = 1 * (2 * 256 * 64 + 256 * 64) + 3 * 324 * 4;
     hipLaunchKernelGGL(stem_wgrad_kernel<bf16_t>, grid, dim3(256), lds, s, (const bf16_t*)dy, lddy, x_nchw, part, B,
                        H, W, Cin, Cout, cdiv(H, 16), cdiv(W, 16));
-  } else if (dtype == S2S_F32) {
+  } else {
     const int lds = 3 * (2 * 256 * 64 + 256 * 64) + 3 * 324 * 4;
     static unsigned long long attr_devs = 0;   // hipFuncSetAttribute is per device
     if (int rc = s2s_allow_dyn_lds(reinterpret_cast<const void*>(stem_wgrad_kernel<float>), lds, &attr_devs)) return rc;
     hipLaunchKernelGGL(stem_wgrad_kernel<float>, grid, dim3(256), lds, s, (const float*)dy, lddy, x_nchw, part, B, H,
                        W, Cin, Cout, cdiv(H, 16), cdiv(W, 16));
-  } else return S2S_ERR_DTYPE;
+  }
   hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3(Cout, cdiv(Cin, 3)), dim3(1024), 0, s, part, 2 * nb, Cout, Cin, dw_oihw, dbias,
                      accumulate);
   S2S_LAUNCH_CHECK();
   return S2S_OK;
+}
+
+}  // namespace
+
+extern "C" int s2s_stem_conv3x3_wgrad(int dtype, const void* dy, int lddy, const float* x_nchw, float* part,
+                                      float* dw_oihw, float* dbias, int accumulate, int B, int H, int W, int Cin,
+                                      int Cout, void* stream) {
+  return stem_wgrad_launch(dtype, dy, lddy, x_nchw, part, dw_oihw, dbias, accumulate, B, H, W, Cin, Cout, stream, false);
+}
+
+// test-facing: the kernel the bf16 production launch replaced, on the same arguments (fp32: the same launch)
+extern "C" int s2s_stem_conv3x3_wgrad_ref(int dtype, const void* dy, int lddy, const float* x_nchw, float* part,
+                                          float* dw_oihw, float* dbias, int accumulate, int B, int H, int W, int Cin,
+                                          int Cout, void* stream) {
+  return stem_wgrad_launch(dtype, dy, lddy, x_nchw, part, dw_oihw, dbias, accumulate, B, H, W, Cin, Cout, stream, true);
+}
+
+// test-facing, no launch: 0 = the reference kernel, 1 = the pipelined kernel, < 0 = the error the launch would return.
+// reference != 0: as s2s_stem_conv3x3_wgrad_ref chooses.
+extern "C" int s2s_stem_wgrad_family(int dtype, int lddy, int B, int H, int W, int Cin, int Cout, int reference) {
+  if (int rc = stem_wgrad_check(dtype, B, H, W, Cin, Cout, lddy)) return rc;
+  return stem_wgrad_family(dtype, reference != 0);
 }
 
 extern "C" int s2s_head_family(int dtype, int B, int H, int W, int C, int Cout, int forward) {

@@ -443,10 +443,17 @@ template <typename T>
 struct UpTaps { Raw8<T> t[2][2]; };          // one source row as loaded: [output column 2 sx + e][tap i0, i1]
 struct UpMix2 { f32x8 e[2]; };               // its horizontal mixes for output columns 2 sx and 2 sx + 1
 
-template <typename T, bool BIAS>
+// AFFINE: x is a convolution's raw output and the kernel up-samples relu(bn(x)) without that activation ever being
+// stored: every tap value v becomes round_T(fmaxf(fmaf(v, scale[c], shift[c]), 0)) as it is widened, the expression and
+// the rounding of bn_relu_apply_kernel, so the result is that of bn_relu_apply followed by this kernel, bit for bit.  The
+// time bias is added after it, as to a stored activation; the zero pad is written as zeros and never sees the affine.
+// A lane's sixteen constants stay in registers: the bf16 no-bias instance compiles to 120 VGPRs (110 without the affine), so
+// it keeps 4 waves per SIMD without scratch; read from LDS per row instead they made the four launches 2 % slower.
+template <typename T, bool BIAS, bool AFFINE>
 __global__ __launch_bounds__(256, sizeof(T) == 2 && !BIAS ? 4 : 2) void upsample2x_fwd_win_kernel(
-    const T* __restrict__ x, int ldx, const float* __restrict__ bias, T* __restrict__ y, int ldy, int B, int Hin, int Win,
-    int Hout, int Wout, int padT, int padL, int C, int band, int nband, int ncol, int nwork) {
+    const T* __restrict__ x, int ldx, const float* __restrict__ bias, const float* __restrict__ scale,
+    const float* __restrict__ shift, T* __restrict__ y, int ldy, int B, int Hin, int Win, int Hout, int Wout, int padT,
+    int padL, int C, int band, int nband, int ncol, int nwork) {
   constexpr unsigned ES = sizeof(T);
   const int cp = C >> 3;
   const int Hu = 2 * Hin, Wu = 2 * Win;
@@ -464,6 +471,9 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 && !BIAS ? 4 : 2) void upsample
   const int sx = cg * WL + slot, piece = chunk * PCB + pc;
   if (sx >= Win || piece >= cp) return;
   const int c8 = piece * 8;
+  float kc0[8], kc1[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { kc0[k] = AFFINE ? scale[c8 + k] : 1.f; kc1[k] = AFFINE ? shift[c8 + k] : 0.f; }
 
   float bv[8];
 #pragma unroll
@@ -491,7 +501,14 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 && !BIAS ? 4 : 2) void upsample
     UpMix2 m;
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-      const f32x8 v0 = widen8(w.t[e][0]), v1 = widen8(w.t[e][1]);
+      f32x8 v0 = widen8(w.t[e][0]), v1 = widen8(w.t[e][1]);
+      if (AFFINE) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          v0.v[k] = to_f32(from_f32<T>(fmaxf(fmaf(v0.v[k], kc0[k], kc1[k]), 0.f)));
+          v1.v[k] = to_f32(from_f32<T>(fmaxf(fmaf(v1.v[k], kc0[k], kc1[k]), 0.f)));
+        }
+      }
 #pragma unroll
       for (int k = 0; k < 8; ++k) m.e[e].v[k] = up_row_mix(ax[e], v0.v[k], v1.v[k], bv[k], k);
     }
@@ -630,8 +647,11 @@ int upsample2x_fwd_check(int ldx, int ldy, int B, int Hin, int Win, int Hout, in
 }
 
 // `reference`: the row-sweep kernel that the register-window kernel replaced (tests compare the two bit for bit)
+// scale / shift (both or neither): the window kernel's affine form; the row-sweep kernel has none, so a launch that
+// would take it is refused (the caller applies bn_relu_apply first)
 int upsample2x_fwd_launch(int dtype, const void* x, int ldx, const float* bias_nc, void* y, int ldy, int B, int Hin,
-                          int Win, int Hout, int Wout, int C, void* stream, bool reference) {
+                          int Win, int Hout, int Wout, int C, void* stream, bool reference,
+                          const float* scale = nullptr, const float* shift = nullptr) {
   if (!x || !y) return S2S_ERR_NULL;
   if (int rc = upsample2x_fwd_check(ldx, ldy, B, Hin, Win, Hout, Wout, C)) return rc;
   if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
@@ -641,15 +661,21 @@ int upsample2x_fwd_launch(int dtype, const void* x, int ldx, const float* bias_n
     const int band = upsample2x_fwd_band(B, Hin, Win, C), nband = cdiv(Hin, band);
     const int ncol = cdiv(Win, 256 / rs_pcb(C)), nwork = B * nband * ncol;
     const dim3 wgrid((unsigned)((long)nwork * cdiv(C / 8, 32)));
-#define S2S_UPW(TT, BB)                                                                                              \
-  hipLaunchKernelGGL((upsample2x_fwd_win_kernel<TT, BB>), wgrid, dim3(256), 0, s, (const TT*)x, ldx, bias_nc, (TT*)y, \
-                     ldy, B, Hin, Win, Hout, Wout, padT, padL, C, band, nband, ncol, nwork)
-    if (dtype == S2S_BF16) { if (bias_nc) S2S_UPW(bf16_t, true); else S2S_UPW(bf16_t, false); }
-    else { if (bias_nc) S2S_UPW(float, true); else S2S_UPW(float, false); }
+#define S2S_UPW(TT, BB, AA)                                                                                         \
+  hipLaunchKernelGGL((upsample2x_fwd_win_kernel<TT, BB, AA>), wgrid, dim3(256), 0, s, (const TT*)x, ldx, bias_nc, scale, \
+                     shift, (TT*)y, ldy, B, Hin, Win, Hout, Wout, padT, padL, C, band, nband, ncol, nwork)
+    if (scale) {
+      if (dtype == S2S_BF16) { if (bias_nc) S2S_UPW(bf16_t, true, true); else S2S_UPW(bf16_t, false, true); }
+      else { if (bias_nc) S2S_UPW(float, true, true); else S2S_UPW(float, false, true); }
+    } else {
+      if (dtype == S2S_BF16) { if (bias_nc) S2S_UPW(bf16_t, true, false); else S2S_UPW(bf16_t, false, false); }
+      else { if (bias_nc) S2S_UPW(float, true, false); else S2S_UPW(float, false, false); }
+    }
 #undef S2S_UPW
     S2S_LAUNCH_CHECK();
     return S2S_OK;
   }
+  if (scale) return S2S_ERR_SHAPE;
   const long rows = (long)B * Hout;
   // rows per workgroup: 4 while that still leaves >= 1024 workgroups (4 per CU), else 2, else 1 (S2S_UP_BAND overrides)
   const int band = up_band_env() > 0 ? up_band_env() : (rows >= 4096 ? 4 : rows >= 2048 ? 2 : 1);
@@ -671,6 +697,17 @@ extern "C" int s2s_upsample2x_bilinear_ac_fwd(int dtype, const void* x, int ldx,
                                               int ldy, int B, int Hin, int Win, int Hout, int Wout, int C,
                                               void* stream) {
   return upsample2x_fwd_launch(dtype, x, ldx, bias_nc, y, ldy, B, Hin, Win, Hout, Wout, C, stream, false);
+}
+
+// The up-sampling of relu(bn(x)) from the convolution's raw output x, with that layer's folded scale / shift (rows 2 and
+// 3 of bn_finalize): the result of s2s_bn_relu_apply followed by s2s_upsample2x_bilinear_ac_fwd, bit for bit, without the
+// activation in between.  Shapes for which s2s_upsample2x_fwd_family answers 0 (the row-sweep kernel) are refused with
+// S2S_ERR_SHAPE.
+extern "C" int s2s_upsample2x_bn_relu_fwd(int dtype, const void* x, int ldx, const float* scale, const float* shift,
+                                          const float* bias_nc, void* y, int ldy, int B, int Hin, int Win, int Hout,
+                                          int Wout, int C, void* stream) {
+  if (!scale || !shift) return S2S_ERR_NULL;
+  return upsample2x_fwd_launch(dtype, x, ldx, bias_nc, y, ldy, B, Hin, Win, Hout, Wout, C, stream, false, scale, shift);
 }
 
 // test-facing: the kernel the production entry point replaced, on the same arguments

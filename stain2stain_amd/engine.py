@@ -244,6 +244,23 @@ class LayerCtx:
 
 
 @dataclass
+class LazyAct:
+    """The activation relu(raw * scale + shift) of a conv + BatchNorm layer that was stopped after its statistics
+    (``lazy_up``): its only reader, the next up-sampling, applies the affine to its loads (``ops.upsample2x_fwd``,
+    ``bn_relu``), so the activation is never stored."""
+    raw: torch.Tensor                   # conv output
+    scale: torch.Tensor                 # rows 2 and 3 of the layer's statistics
+    shift: torch.Tensor
+
+    @property
+    def shape(self):
+        return self.raw.shape
+
+    def materialise(self) -> torch.Tensor:
+        return ops.bn_relu_apply(self.raw, self.scale, self.shift)[0]
+
+
+@dataclass
 class EncCtx:
     dtype: torch.dtype
     x_nchw: torch.Tensor
@@ -336,6 +353,20 @@ def _conv_bn_relu(cb: ConvBN, x0, x1, dtype, training: bool, want_pool: bool = F
         act, _ = ops.conv3x3(x0, x1, cb.packed(dtype)[0], bias, cb.cout, scale=ss[0], shift=ss[1], relu=True)
         pooled = ops.maxpool2(act) if want_pool else None
     return None, act, pooled
+
+
+def _conv_bn_lazy(cb: ConvBN, x0, x1, dtype):
+    """Training mode: conv + BatchNorm stopped after the statistics, as ``_conv_bn_tail`` does -- the backward works from
+    ``raw`` and ``stats`` alone.  Returns (LayerCtx with ``act = None``, LazyAct)."""
+    raw, st, count, sx = _conv_bn_stats(cb, x0, x1, dtype)
+    return LayerCtx(x0, x1, raw, None, st, count if sx is not None else None, sx), LazyAct(raw, st[2], st[3])
+
+
+def _upsample_into(x, up: torch.Tensor, tbias) -> None:
+    if isinstance(x, LazyAct):
+        ops.upsample2x_fwd(x.raw, up, tbias, bn_relu=(x.scale, x.shift))
+    else:
+        ops.upsample2x_fwd(x, up, tbias)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -476,8 +507,11 @@ def _conv_bn_tail_bwd(dec, cb: ConvBN, lc: LayerCtx, tail, grads, accumulate: bo
 # encoder
 # ------------------------------------------------------------------------------------------------
 def encoder_forward(blocks: Sequence[Tuple[ConvBN, ConvBN]], x_nchw: torch.Tensor, dtype: torch.dtype,
-                    training: bool) -> EncCtx:
-    """blocks[l] = (conv1, conv2) of level l (l = 0 is ``inc``).  Keeps every level's activation."""
+                    training: bool, lazy_up: bool = False) -> EncCtx:
+    """blocks[l] = (conv1, conv2) of level l (l = 0 is ``inc``).  Keeps every level's activation.
+    ``lazy_up`` (training mode, more than one level): the bottleneck, which only the decoder's first up-sampling reads,
+    is not stored -- ``ctx.feats[-1]`` is a ``LazyAct`` for ``decoder_forward`` and the layer's LayerCtx has
+    ``act = None``."""
     ctx = EncCtx(dtype, x_nchw)
     nlev = len(blocks)
     repack_stale([cb for l, pair in enumerate(blocks) for j, cb in enumerate(pair)
@@ -485,7 +519,10 @@ def encoder_forward(blocks: Sequence[Tuple[ConvBN, ConvBN]], x_nchw: torch.Tenso
     inp = x_nchw
     for l, (c1, c2) in enumerate(blocks):
         lc1, a1, _ = _conv_bn_relu(c1, inp, None, dtype, training, stem=(l == 0))
-        lc2, a2, pooled = _conv_bn_relu(c2, a1, None, dtype, training, want_pool=(l + 1 < nlev))
+        if lazy_up and training and nlev > 1 and l == nlev - 1:
+            (lc2, a2), pooled = _conv_bn_lazy(c2, a1, None, dtype), None
+        else:
+            lc2, a2, pooled = _conv_bn_relu(c2, a1, None, dtype, training, want_pool=(l + 1 < nlev))
         ctx.layers.append((lc1, lc2))
         ctx.feats.append(a2)
         inp = pooled
@@ -518,12 +555,17 @@ def encoder_backward(blocks: Sequence[Tuple[ConvBN, ConvBN]], ctx: EncCtx, dfeat
 # decoder
 # ------------------------------------------------------------------------------------------------
 def decoder_forward(dec, bottleneck: torch.Tensor, skips: Sequence[torch.Tensor], t_emb: torch.Tensor,
-                    dtype: torch.dtype, training: bool, with_head: bool = True, fuse_tail: bool = False) -> DecCtx:
+                    dtype: torch.dtype, training: bool, with_head: bool = True, fuse_tail: bool = False,
+                    lazy_up: bool = False) -> DecCtx:
     """dec: FlowMatchingDecoder container (time_mlp, time_proj, up_blocks, outc).  with_head=False stops at the
     last activation (ctx.lows[-1]); the fused head+loss kernel of the training step takes it from there.
     ``fuse_tail`` (training mode, with_head=False, channel counts ``ops.tail_fusable`` takes, no SyncBatchNorm): stop
     one step earlier, after the last layer's statistics -- its LayerCtx has ``act = None``, ctx.lows[-1] is None and
-    ``decoder_tail_loss`` takes it from there.  Anything else keeps the ordinary chain."""
+    ``decoder_tail_loss`` takes it from there.  Anything else keeps the ordinary chain.
+    ``lazy_up`` (training mode): the second conv of every Up block but the last stops after its statistics too; its
+    activation, which only the next block's up-sampling reads, is never stored (``LazyAct``: that up-sampling applies
+    BatchNorm + ReLU to its loads, same bits).  Those layers have ``act = None`` and their entry of ``ctx.lows`` is the
+    LazyAct.  ``bottleneck`` may be one (``encoder_forward(..., lazy_up=True)``) whatever this flag says."""
     fuse_tail = (fuse_tail and training and not with_head and len(dec.up_blocks) > 0
                  and ops.tail_fusable(dec.up_blocks[-1][1].cout, dec.outc.weight.shape[0]))
     ctx = DecCtx(dtype, t_emb)
@@ -538,15 +580,19 @@ def decoder_forward(dec, bottleneck: torch.Tensor, skips: Sequence[torch.Tensor]
     x = bottleneck
     for i, ((c1, c2), skip) in enumerate(zip(dec.up_blocks, skips)):
         B, Hs, Ws, _ = skip.shape
-        up = torch.empty((B, Hs, Ws, x.shape[3]), dtype=dtype, device=x.device)
-        ops.upsample2x_fwd(x, up, tbias if i == 0 else None)
+        up = torch.empty((B, Hs, Ws, x.shape[3]), dtype=dtype, device=skip.device)
+        _upsample_into(x, up, tbias if i == 0 else None)
         lc1, a1, _ = _conv_bn_relu(c1, skip, up, dtype, training)
         if fuse_tail and i == len(dec.up_blocks) - 1:
             lc2, a2 = _conv_bn_tail(c2, a1, dtype)
+        elif lazy_up and training and i < len(dec.up_blocks) - 1:
+            lc2, a2 = _conv_bn_lazy(c2, a1, None, dtype)
         else:
             lc2, a2, _ = _conv_bn_relu(c2, a1, None, dtype, training)
         ctx.lows.append(x); ctx.ups.append(up); ctx.skips.append(skip); ctx.layers.append((lc1, lc2))
         x = a2
+    if isinstance(x, LazyAct):      # (a decoder without Up blocks: the head reads the bottleneck itself)
+        x = x.materialise()
     ctx.lows.append(x)  # head input
     if not with_head:
         return ctx

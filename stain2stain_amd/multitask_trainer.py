@@ -104,6 +104,9 @@ class MultiTaskTrainer:
         self._side = ops.side_stream_for(dev)
         self.overlap_wgrad = True
         self.fuse_tail = True           # the flow decoder's tail without its last activation, as CFMTrainer.fuse_tail
+        # both decoders: no stored activation in front of an up-sampling but the first, as CFMTrainer.lazy_up.  The two
+        # encoder passes keep their bottleneck: the step-wise suite reads every encoder layer's activation from this step
+        self.lazy_up = True
         self._group = 0
         self._eval_owner = object()         # evaluate()'s workspaces, released by close()
         self._generation = evaluation.GenerationEval()      # evaluate_generation()'s velocities and captured steps
@@ -136,14 +139,15 @@ class MultiTaskTrainer:
         eps_noise = torch.randn_like(x0) if self.sigma != 0.0 else None
         xt, ut = ops.cfm_sample(x0, x1, t, self.sigma, eps_noise)
         # forward: encoder(xt) -> flow head, then encoder(source) -> mask head (the reference's order, :228-236)
+        lazy = self.lazy_up and not want_outputs
         ectx1 = engine.encoder_forward(enc._blocks, xt, dt, True)
         temb = ops.time_embedding(t, self.time_emb_dim)
         f1 = ectx1.feats
         dctx_f = engine.decoder_forward(fdec, f1[-1], f1[:-1][::-1], temb, dt, True, with_head=False,
-                                        fuse_tail=self.fuse_tail and not want_outputs)
+                                        fuse_tail=self.fuse_tail and not want_outputs, lazy_up=lazy)
         ectx2 = engine.encoder_forward(enc._blocks, x0, dt, True)
         f2 = ectx2.feats
-        dctx_s = engine.decoder_forward(sdec, f2[-1], f2[:-1][::-1], None, dt, True)
+        dctx_s = engine.decoder_forward(sdec, f2[-1], f2[:-1][::-1], None, dt, True, lazy_up=lazy)
         logits = dctx_s.v
         if dctx_f.lows[-1] is None:     # fused tail (engine.decoder_tail_loss)
             g_head = None

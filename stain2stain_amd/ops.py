@@ -416,15 +416,26 @@ def stem_fwd(x_nchw: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]
 
 @_timed("stem_wgrad")
 def stem_wgrad(dy: torch.Tensor, x_nchw: torch.Tensor, dw: torch.Tensor, dbias: Optional[torch.Tensor],
-               accumulate: bool = False) -> None:
+               accumulate: bool = False, _reference: bool = False) -> None:
+    """``_reference`` (tests only): the kernel that the pipelined bf16 kernel replaced; same bits."""
     B, H, W, cout = dy.shape
     cin = x_nchw.shape[1]
     pdy, lddy = _nhwc(dy)
     nb = _L().s2s_stem_wgrad_blocks(B, H, W)
     part = torch.empty(((cin + 2) // 3, 2 * nb, cout, 32), dtype=torch.float32, device=dy.device)
-    rc = _L().s2s_stem_conv3x3_wgrad(_dt(dy), pdy, lddy, _f32(x_nchw), _f32(part), _f32(dw), _f32(dbias),
-                                     int(accumulate), B, H, W, cin, cout, _stream())
+    fn = _L().s2s_stem_conv3x3_wgrad_ref if _reference else _L().s2s_stem_conv3x3_wgrad
+    rc = fn(_dt(dy), pdy, lddy, _f32(x_nchw), _f32(part), _f32(dw), _f32(dbias), int(accumulate), B, H, W, cin, cout,
+            _stream())
     _native.check(rc, "stem_conv3x3_wgrad")
+
+
+def stem_wgrad_family(dy: torch.Tensor, x_nchw: torch.Tensor, _reference: bool = False) -> int:
+    """Which kernel ``stem_wgrad`` launches for these tensors (tests): 0 the reference kernel, 1 the pipelined one."""
+    B, H, W, cout = dy.shape
+    rc = _L().s2s_stem_wgrad_family(_dt(dy), _nhwc(dy)[1], B, H, W, x_nchw.shape[1], cout, int(_reference))
+    if rc < 0:
+        _native.check(rc, "stem_wgrad_family")
+    return rc
 
 
 @_timed("head_fwd")
@@ -642,12 +653,28 @@ def bn_relu_bwd(g1: Optional[torch.Tensor], gp: Optional[torch.Tensor], x: torch
 # ------------------------------------------------------------------------------------------------
 @_timed("upsample2x_fwd")
 def upsample2x_fwd(x: torch.Tensor, out: torch.Tensor, bias_nc: Optional[torch.Tensor] = None,
-                   _reference: bool = False) -> None:
-    """``_reference`` (tests only): the row-sweep kernel that the register-window kernel replaced; same bits."""
+                   _reference: bool = False, bn_relu: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> None:
+    """``_reference`` (tests only): the row-sweep kernel that the register-window kernel replaced; same bits.
+    ``bn_relu`` = (scale, shift): ``x`` is a convolution's raw output and what is up-sampled is
+    ``bn_relu_apply(x, scale, shift)``, which the register-window kernel applies to its loads (same bits, the activation
+    is never stored).  Shapes that kernel does not take run ``bn_relu_apply`` into a scratch tensor first."""
     B, Hin, Win, C = x.shape
     _, Hout, Wout, Co = out.shape
     if Co != C or out.dtype != x.dtype:
         raise RuntimeError("stain2stain_amd: upsample output slice mismatch")
+    if bn_relu is not None:
+        scale, shift = bn_relu
+        if scale.numel() != C or shift.numel() != C:
+            raise RuntimeError("stain2stain_amd: upsample scale / shift do not match the channel count")
+        if _reference or upsample2x_fwd_family(x, out) != 1:
+            x, _ = bn_relu_apply(x, scale, shift)
+        else:
+            px, ldx = _nhwc(x)
+            py, ldy = _nhwc(out)
+            rc = _L().s2s_upsample2x_bn_relu_fwd(_dt(x), px, ldx, _f32(scale), _f32(shift), _f32(bias_nc), py, ldy, B,
+                                                 Hin, Win, Hout, Wout, C, _stream())
+            _native.check(rc, "upsample2x_fwd")
+            return
     px, ldx = _nhwc(x)
     py, ldy = _nhwc(out)
     fn = _L().s2s_upsample2x_bilinear_ac_fwd_ref if _reference else _L().s2s_upsample2x_bilinear_ac_fwd

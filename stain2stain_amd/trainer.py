@@ -138,6 +138,10 @@ class CFMTrainer:
         # bn_relu_apply -> head_loss_fused -> bn_relu_bwd, as does a forward_backward that is asked for the velocity
         # (want_v: the inspecting call, which leaves every layer's activation in its context)
         self.fuse_tail = True
+        # the activations that only an up-sampling reads (the bottleneck, the second conv of every Up block but the
+        # last) are not stored: the up-sampling applies BatchNorm + ReLU to its loads (engine.LazyAct), same bits.  False,
+        # or the inspecting call (want_v), keeps them
+        self.lazy_up = True
         self.graph = graph
         self._graph_step = CapturedStep()
         self._ema = None
@@ -180,11 +184,12 @@ class CFMTrainer:
         eps_noise = torch.randn_like(x0) if self.sigma != 0.0 else None
         xt, ut = ops.cfm_sample(x0, x1, t, self.sigma, eps_noise)
         with engine.sync_batchnorm(self._sync_bn):
-            ectx = engine.encoder_forward(enc._blocks, xt, dt, True)
+            lazy = self.lazy_up and not want_v
+            ectx = engine.encoder_forward(enc._blocks, xt, dt, True, lazy_up=lazy)
             temb = ops.time_embedding(t, net.time_embedding.dim)
             feats = ectx.feats
             dctx = engine.decoder_forward(dec, feats[-1], feats[:-1][::-1], temb, dt, True, with_head=False,
-                                          fuse_tail=self.fuse_tail and not want_v)
+                                          fuse_tail=self.fuse_tail and not want_v, lazy_up=lazy)
         if dctx.lows[-1] is None:       # fused tail: the loss and the head's gradients straight from the last conv output
             g_head = None
             loss, v = engine.decoder_tail_loss(dec, dctx, ut, self.grads_dec, want_v=want_v)
