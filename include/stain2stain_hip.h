@@ -592,6 +592,53 @@ int s2s_morph_boundary_finalize(const int* scratch, int B, int H, int W, int* ma
                                 long* within, long* boundary_pred, long* boundary_target, int* valid, double* hausdorff,
                                 double* hd, double* assd, double* surface_dice, void* stream);
 
+/* ---- stain object morphometry: per-object shape, thickness and intensity (object_features.hip) ---
+ * labels: int [B][H][W], dense, as s2s_objects_label writes them: 0 = background or a dropped object, objects 1..count.
+ *   M = max_objects >= 1; objects numbered above M are not tabulated, but where a neighbour rule asks whether a label
+ *   differs they are a different label.  H, W <= 32767 and B <= 65535; anything beyond is refused with the shape status
+ *   before any launch.  The CALLER ZEROES count and every table; rows at or beyond min(count, M) are not touched, and a
+ *   sample's values do not depend on its batch mates.  Every table is an integer, added to or maxed into by integer
+ *   atomics, so the bits do not depend on the order.
+ * s2s_objfeat_shape: count int [B] = the largest label of the sample.  Per object (row = label - 1): area long [B][M];
+ *   bbox int [B][M][4] = y0, x0, y1, x1, end-exclusive; moments long [B][M][5] = sum y, sum x, sum y^2, sum x^2, sum yx
+ *   (each below 2^61); edges long = the crack length: the pairs (pixel of the object, one of its four neighbours) whose
+ *   neighbour carries another label or lies outside the image; boundary long = the object's pixels with at least one
+ *   such neighbour; border int = 1 iff the object has a pixel in the first or last row or column.  d2 (optional): the
+ *   int [B][H][W] map of s2s_morph_edt; given, max_d2 int [B][M] = its maximum over the object's pixels.  Two launches.
+ * s2s_objfeat_intensity_u8 / _f32: images, od_table (256 HOST floats) and unmix (HOST floats, m[3 * channel + stain];
+ *   only the first nine are read) as s2s_stain_mask_u8 / _f32.  Per pixel whose label is in 1..M: c = ((od_r m_rk) +
+ *   (od_g m_gk)) + (od_b m_bk) in fp32, every operation rounded on its own; q = min((int)rintf(fmaxf(c, 0) * 1024),
+ *   4095); sum_q long [B][M] += q, sum_q2 long [B][M] += q^2, max_q int [B][M] = max(max_q, q).  No tissue gate.  The
+ *   bands of a region accumulate in the same tables.  One launch.
+ * s2s_objfeat_finalize: out double [B][M][15], one thread per object, fp64, no contraction, in this order (A = area, Ad =
+ *   (double)A, A2 = Ad * Ad; N(s2, s, s') = A * s2 - s * s' formed exactly in 128 bits from 64 x 64 -> 128 multiplies,
+ *   converted to double once, sign applied after):
+ *     0, 1  centroid y, x = (double)sum_y / Ad, (double)sum_x / Ad
+ *     2     equivalent_diameter = sqrt((4 * Ad) / pi)
+ *     3..5  mu_yy = N(sum_y2, sum_y, sum_y) / A2, mu_xx = N(sum_x2, sum_x, sum_x) / A2, mu_yx = N(sum_yx, sum_y, sum_x) / A2
+ *           t = mu_xx + mu_yy; d = mu_xx - mu_yy; root = sqrt(d * d + 4 * (mu_yx * mu_yx));
+ *           l1 = max(0.5 * (t + root), 0); l2 = max(0.5 * (t - root), 0)
+ *     6, 7  major_axis = 4 * sqrt(l1), minor_axis = 4 * sqrt(l2)
+ *     8     eccentricity = sqrt(max(1 - l2 / l1, 0)), 0 when l1 == 0
+ *     9     orientation = 0.5 * atan2(2 * mu_yx, d), 0 when both arguments are 0
+ *     10    compactness = (4 pi * Ad) / (E * E), E = (double)edges, 4 pi = 12.566370614359172
+ *     11    mean_conc = ((double)sum_q / Ad) / 1024
+ *     12    std_conc = sqrt(max(N(sum_q2, sum_q, sum_q) / A2, 0)) / 1024
+ *     13    max_conc = (double)max_q / 1024
+ *     14    inscribed_radius = sqrt((double)max_d2), inf when max_d2 == 2^31 - 1
+ *   11..13 are 0 when sum_q is null, 14 when max_d2 is null.  Rows at or beyond min(count, M), and rows of area 0, are 0. */
+int s2s_objfeat_shape(const int* labels, const int* d2, int B, int H, int W, int max_objects, int* count, long* area,
+                      int* bbox, long* moments, long* edges, long* boundary, int* border, int* max_d2, void* stream);
+int s2s_objfeat_intensity_u8(const int* labels, const void* img, long pitch, long img_stride, int B, int band_top,
+                             int band_h, int H, int W, int max_objects, const float* od_table, const float* unmix,
+                             int stain, long* sum_q, long* sum_q2, int* max_q, void* stream);
+int s2s_objfeat_intensity_f32(const int* labels, const float* img, int B, int H, int W, int max_objects,
+                              const float* od_table, const float* unmix, int stain, long* sum_q, long* sum_q2, int* max_q,
+                              void* stream);
+int s2s_objfeat_finalize(const int* count, const long* area, const long* moments, const long* edges, const long* sum_q,
+                         const long* sum_q2, const int* max_q, const int* max_d2, int B, int max_objects, double* out,
+                         void* stream);
+
 /* ---- fused paired augmentation: crop, D4, stain jitter, masks (augment.hip) --------
  * Geometry: params is a DEVICE int [B][param_cols], param_cols 4 or 5 = (top, left, hflip, vflip[, transpose]); with
  *   f[a][b] = img[n][top + (vflip ? S-1-a : a)][left + (hflip ? S-1-b : b)], out[y][x] = transpose ? f[x][y] : f[y][x].

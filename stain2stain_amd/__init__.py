@@ -34,6 +34,8 @@ from .registration import (overlap_boxes, region_shift_field, register_pairs, re
 from .warp import clean_shift_field, register_region, warp_region
 from .qc import qc_keep, region_qc, region_qc_map, tile_qc, window_sums
 from .morphology import distance_transform, fill_holes, mask_boundary, mask_boundary_agreement, mask_morphology
+from .object_features import (object_feature_summary, object_features, region_stain_object_features,
+                              stain_object_features)
 
 __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeEmbedding", "FlowUNet",
            "ConditionalFlowMatcher", "ConditionalFlowMatchingModule", "MultiTaskFlowMatchingModule", "euler_generate", "dopri5_generate", "euler_integrate", "dopri5_integrate", "SolverConfig", "GraphedVelocity",
@@ -51,4 +53,5 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "sample_crop_params_within", "registered_quality", "region_shift_field",
            "clean_shift_field", "warp_region", "register_region",
            "tile_qc", "region_qc", "region_qc_map", "qc_keep", "window_sums",
-           "distance_transform", "mask_morphology", "fill_holes", "mask_boundary", "mask_boundary_agreement"]
+           "distance_transform", "mask_morphology", "fill_holes", "mask_boundary", "mask_boundary_agreement",
+           "object_features", "stain_object_features", "region_stain_object_features", "object_feature_summary"]
