@@ -639,6 +639,27 @@ int s2s_objfeat_finalize(const int* count, const long* area, const long* moments
                          const long* sum_q2, const int* max_q, const int* max_d2, int B, int max_objects, double* out,
                          void* stream);
 
+/* ---- splitting touching objects at their necks: watershed on the distance map (split.hip) ---
+ * d2: int [B][H][W], dense, the squared distance to the background as s2s_morph_edt(to_foreground = 0) writes it;
+ *   foreground iff d2 > 0 (2^31 - 1 everywhere in a sample without background).  H, W <= 32767 and B <= 65535; anything
+ *   beyond is refused with the shape status before any launch.  A sample's values do not depend on its batch mates.
+ * s2s_split_words(B, H, W): the int32 words of scratch s2s_split_label needs (4 H W + ceil(H W / 1024) per sample; the
+ *   scratch must be 8-byte aligned, S2S_ERR_ALIGN otherwise).  Negative: a status code.
+ * s2s_split_label: key(p) = (d2[p], y W + x), compared lexicographically; neighbours = the 4 or 8 (connectivity)
+ *   foreground neighbours inside the image.  up(p) = the neighbour of largest key if it exceeds key(p), else p; a basin
+ *   is the set of pixels whose up-chain ends in the same root r, its peak P = d2[r].  Over all neighbouring pixels (p, q)
+ *   with a = root(p) != b = root(q) and key(b) > key(a), best(a) = the lexicographic maximum of (min(d2[p], d2[q]), b);
+ *   basin a links to that b iff P(a) <= core2 or (long)m << 20 >= (long)neck_q * neck_q * P(a), neck_q in 0..1024 (the
+ *   neck ratio times 1024), core2 >= 0.  The links form a forest; a part is one of its trees.  One round, no
+ *   re-evaluation.  basins int [B] = the number of basins (written).  From there on exactly s2s_objects_label with
+ *   "part" for "object": labels, count (written), kept_pixels, largest, size_hist and the tables (the caller zeroes
+ *   them), min_area and max_objects as there.  Exact and independent of scheduling: every choice is a maximum over a
+ *   strict total order.  Thirteen launches, no host synchronisation. */
+long s2s_split_words(int B, int H, int W);
+int s2s_split_label(const int* d2, int B, int H, int W, int connectivity, int neck_q, int core2, int min_area,
+                    int max_objects, int* scratch, int* labels, int* count, int* basins, long* kept_pixels, int* largest,
+                    long* size_hist, int* tab_area, int* tab_bbox, long* tab_sums, void* stream);
+
 /* ---- fused paired augmentation: crop, D4, stain jitter, masks (augment.hip) --------
  * Geometry: params is a DEVICE int [B][param_cols], param_cols 4 or 5 = (top, left, hflip, vflip[, transpose]); with
  *   f[a][b] = img[n][top + (vflip ? S-1-a : a)][left + (hflip ? S-1-b : b)], out[y][x] = transpose ? f[x][y] : f[y][x].

@@ -36,6 +36,7 @@ from .qc import qc_keep, region_qc, region_qc_map, tile_qc, window_sums
 from .morphology import distance_transform, fill_holes, mask_boundary, mask_boundary_agreement, mask_morphology
 from .object_features import (object_feature_summary, object_features, region_stain_object_features,
                               stain_object_features)
+from .split import label_agreement, split_objects, stain_object_split
 
 __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeEmbedding", "FlowUNet",
            "ConditionalFlowMatcher", "ConditionalFlowMatchingModule", "MultiTaskFlowMatchingModule", "euler_generate", "dopri5_generate", "euler_integrate", "dopri5_integrate", "SolverConfig", "GraphedVelocity",
@@ -54,4 +55,5 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "clean_shift_field", "warp_region", "register_region",
            "tile_qc", "region_qc", "region_qc_map", "qc_keep", "window_sums",
            "distance_transform", "mask_morphology", "fill_holes", "mask_boundary", "mask_boundary_agreement",
-           "object_features", "stain_object_features", "region_stain_object_features", "object_feature_summary"]
+           "object_features", "stain_object_features", "region_stain_object_features", "object_feature_summary",
+           "split_objects", "stain_object_split", "label_agreement"]

@@ -19,7 +19,9 @@ ABLATE_LIB_PATH = os.path.join(HERE, "libstain2stain_hip_ablate.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "stain2stain_hip.h")
 SOURCES = ["conv3x3_mfma.hip", "conv3x3_wgrad_mfma.hip", "conv_small.hip", "conv_edge.hip", "norm_act.hip", "resample.hip",
            "flow.hip", "ode.hip", "optim.hip", "input_pipeline.hip", "seg_loss.hip", "eval_metrics.hip", "loss_variants.hip", "instnorm.hip", "pix2pix.hip",
-           "region.hip", "image_metrics.hip", "stain_quant.hip", "stain_norm.hip", "objects.hip", "augment.hip", "registration.hip", "warp.hip", "qc.hip", "morphology.hip", "runtime.hip", "object_features.hip"]
+           "region.hip", "image_metrics.hip", "stain_quant.hip", "stain_norm.hip", "objects.hip", "augment.hip", "registration.hip", "warp.hip", "qc.hip", "morphology.hip", "runtime.hip", "object_features.hip", "split.hip"]
+
+HEADERS = ["common.h", "objects_number.h"]     # csrc headers: a change to one rebuilds every object
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -39,7 +41,7 @@ def needs_build(lib_path: str = None) -> bool:
     if not os.path.exists(lib_path):
         return True
     t = os.path.getmtime(lib_path)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "common.h")]
+    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS]
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 
@@ -61,12 +63,12 @@ def _build_to(lib_path: str, objdir: str, extra: List[str], force: bool, verbose
     flags = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result", *extra]
     procs = []
     objs = []
+    headers = max(os.path.getmtime(os.path.join(CSRC, h)) for h in HEADERS)
     for src in SOURCES:
         obj = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(obj)
         srcp = os.path.join(CSRC, src)
-        if (not force and os.path.exists(obj) and os.path.getmtime(obj) > os.path.getmtime(srcp)
-                and os.path.getmtime(obj) > os.path.getmtime(os.path.join(CSRC, "common.h"))):
+        if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(srcp), headers):
             continue
         cmd = [hipcc(), *flags, "-c", srcp, "-o", obj]
         if verbose:

@@ -29,11 +29,15 @@
 // numbering the kept roots in raster order is numbering the objects by first pixel.  find() terminates because parents
 // strictly decrease.  Everything accumulated is an integer, so atomics in any order give the same bits.
 //
+// The passes from zero on are the numbering stage, s2s_number_sets of objects_number.h: it takes any image of first-pixel
+// raster indices, and s2s_split_label (split.hip) numbers its parts with the same launches.
+//
 // The scratch holds the previous call's contents: every word a pass reads was written by an earlier pass of the same call.
 // Nothing here allocates, synchronises or reads back to the host, so the launches may be captured.
 #include <limits.h>
 
 #include "common.h"
+#include "objects_number.h"
 
 namespace {
 
@@ -441,6 +445,25 @@ long ob_flag_words(long hw) { return (hw / 2 + 2 + 31) / 32; }
 
 }  // namespace
 
+// ---- the numbering stage (objects_number.h): zero, area, count, scan, number, relabel -----------------------------------
+long s2s_number_chunks(long hw) { return (hw + OB_CHUNK - 1) / OB_CHUNK; }
+
+void s2s_number_sets(int* labels, int* area, int* chunk, int B, int H, int W, int min_area, int max_objects, int* count,
+                     long long* kept_pixels, int* largest, long long* size_hist, int* tab_area, int* tab_bbox,
+                     long long* tab_sums, hipStream_t s) {
+  const long hw = (long)H * W, nchunk = s2s_number_chunks(hw);
+  const ObTable tb{max_objects, tab_area, tab_bbox, tab_sums};
+  const dim3 pix((unsigned)((hw + 255) / 256), (unsigned)B), chunks((unsigned)nchunk, (unsigned)B);
+  hipLaunchKernelGGL(ob_zero_kernel, pix, dim3(256), 0, s, labels, hw, area);
+  hipLaunchKernelGGL(ob_area_kernel, pix, dim3(256), 0, s, labels, hw, area);
+  hipLaunchKernelGGL(ob_count_kernel, chunks, dim3(256), 0, s, labels, area, hw, min_area, nchunk, chunk);
+  hipLaunchKernelGGL(ob_scan_kernel, dim3((unsigned)B), dim3(256), 0, s, chunk, nchunk, count);
+  hipLaunchKernelGGL(ob_number_kernel, chunks, dim3(256), 0, s, labels, area, hw, min_area, nchunk, chunk, kept_pixels,
+                     largest, size_hist, tb);
+  hipLaunchKernelGGL(ob_relabel_kernel, dim3((unsigned)cdiv(W, 256), (unsigned)(H < 65535 ? H : 65535), (unsigned)B),
+                     dim3(256), 0, s, labels, area, H, W, tb);
+}
+
 extern "C" long s2s_objects_words(int B, int H, int W) {
   if (!ob_shape_ok(B, H, W)) return S2S_ERR_SHAPE;
   const long hw = (long)H * W;
@@ -464,30 +487,22 @@ extern "C" int s2s_objects_label(const void* mask, long pitch, long img_stride, 
     return S2S_ERR_SHAPE;
   static_assert(sizeof(long) == sizeof(long long), "int64 counts");
   hipStream_t s = (hipStream_t)stream;
-  const long hw = (long)H * W, nchunk = (hw + OB_CHUNK - 1) / OB_CHUNK;
+  const long hw = (long)H * W;
   const int tiles_y = cdiv(H, OT_H), tiles_x = cdiv(W, OT_W);
   const long tiles = (long)tiles_y * tiles_x, pix_blocks = (hw + 255) / 256;
   if (tiles > 0x7fffffffL) return S2S_ERR_SHAPE;
   int* parent = scratch;
   int* chunk = scratch + (long)B * hw;
   const ObMask k{(const unsigned char*)mask, pitch, img_stride, fg_bits, H, W};
-  const ObTable tb{max_objects, tab_area, tab_bbox, (long long*)tab_sums};
   const int conn8 = connectivity == 8;
   hipLaunchKernelGGL(ob_local_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(256), 0, s, k, tiles_x, conn8, parent);
   const long n_h = (long)(tiles_y - 1) * W, n_v = (long)(tiles_x - 1) * H;
   if (n_h + n_v > 0)
     hipLaunchKernelGGL(ob_merge_kernel, dim3((unsigned)((n_h + n_v + 255) / 256), (unsigned)B), dim3(256), 0, s, k, n_h,
                        n_v, conn8, parent);
-  const dim3 pix((unsigned)pix_blocks, (unsigned)B), chunks((unsigned)nchunk, (unsigned)B);
-  hipLaunchKernelGGL(ob_flatten_kernel, pix, dim3(256), 0, s, parent, hw, labels);
-  hipLaunchKernelGGL(ob_zero_kernel, pix, dim3(256), 0, s, labels, hw, parent);
-  hipLaunchKernelGGL(ob_area_kernel, pix, dim3(256), 0, s, labels, hw, parent);
-  hipLaunchKernelGGL(ob_count_kernel, chunks, dim3(256), 0, s, labels, parent, hw, min_area, nchunk, chunk);
-  hipLaunchKernelGGL(ob_scan_kernel, dim3((unsigned)B), dim3(256), 0, s, chunk, nchunk, count);
-  hipLaunchKernelGGL(ob_number_kernel, chunks, dim3(256), 0, s, labels, parent, hw, min_area, nchunk, chunk,
-                     (long long*)kept_pixels, largest, (long long*)size_hist, tb);
-  hipLaunchKernelGGL(ob_relabel_kernel, dim3((unsigned)cdiv(W, 256), (unsigned)(H < 65535 ? H : 65535), (unsigned)B),
-                     dim3(256), 0, s, labels, parent, H, W, tb);
+  hipLaunchKernelGGL(ob_flatten_kernel, dim3((unsigned)pix_blocks, (unsigned)B), dim3(256), 0, s, parent, hw, labels);
+  s2s_number_sets(labels, parent, chunk, B, H, W, min_area, max_objects, count, (long long*)kept_pixels, largest,
+                  (long long*)size_hist, tab_area, tab_bbox, (long long*)tab_sums, s);
   S2S_LAUNCH_CHECK();
   return S2S_OK;
 }
