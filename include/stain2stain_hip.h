@@ -43,7 +43,9 @@ extern "C" {
  * (sum, sum of squares) of the stored values per output channel and producing workgroup, for BatchNorm
  * (channel-major, the layout s2s_bn_finalize reads).  ep_scale/ep_shift
  * (optional, both or neither) and relu: y = relu?((acc + bias) * scale + shift) -- eval-mode BatchNorm
- * folded into the epilogue. */
+ * folded into the epilogue.  relu without scale/shift: y = relu(acc + bias), in bf16 and in fp32 alike, with
+ * statistics (of the values as stored) and with a split-K workspace too; such a bf16 launch runs on the per-tap
+ * kernel (the plan of the same launch with a bias) and may store a zero as -0. */
 int s2s_conv3x3_stat_blocks(int dtype, int B, int H, int W, int Cout);
 int s2s_conv3x3_nhwc(int dtype, const void* x0, int ld0, int c0, const void* x1, int ld1, int c1,
                      const void* w_packed, const float* bias, void* y, int ldy, float* stat_part,
@@ -77,6 +79,15 @@ int s2s_conv3x3_staged(int dtype, int B, int H, int W, int Cout, int c0, int c1,
  * the launch is refused.  Tests pin the kernel a case was written for with it. */
 int s2s_conv3x3_family(int dtype, int B, int H, int W, int Cout, int c0, int c1, int ld0, int ld1, int ldy, int has_bias,
                        int has_affine, int stats, int stat_rows, int kwork);
+/* Diagnostic: the whole plan behind s2s_conv3x3_family, from the host code the launch itself dispatches on (nothing is
+ * launched): out[9] = {family, cfg, gx, gy, grid, xsp, xsn, ksplit, stat_rows}.  cfg: the tile, bf16 0..7 = 8x32x128,
+ * 8x32x64, 4x32x128, 4x32x64, 16x16x128, 16x16x64, 8x16x128, 8x16x64 (rows x columns x channels), fp32 0 = 4x32x64,
+ * 1 = 8x16x64; the staged families tile 16x32x64 whatever cfg says.  gx x gy: pixel tiles x channel tiles of the
+ * family's tile.  grid: workgroups of the staged and persistent families (0: the launch is gx x gy x ksplit).  xsp x xsn:
+ * the XCD cut (0 x 1: plain order; the staged families report 8 x 1 or 0 x 1).  stat_rows: rows per channel of
+ * stat_part.  Returns 0, or the negative status of a refused launch. */
+int s2s_conv3x3_plan(int dtype, int B, int H, int W, int Cout, int c0, int c1, int ld0, int ld1, int ldy, int has_bias,
+                     int has_affine, int stats, int stat_rows, int kwork, int* out);
 int s2s_conv3x3_nhwc_s(int dtype, const void* x0, int ld0, int c0, const void* x1, int ld1, int c1, const void* w_packed,
                        const float* bias, void* y, int ldy, float* stat_part, int stat_rows, const float* ep_scale,
                        const float* ep_shift, int relu, float* kwork, int B, int H, int W, int Cout, void* stream);

@@ -2612,10 +2612,9 @@ extern "C" int s2s_conv3x3_staged(int dtype, int B, int H, int W, int Cout, int 
   return f == kStageResident ? 2 : f == kStageStream ? 1 : 0;
 }
 
-extern "C" int s2s_conv3x3_family(int dtype, int B, int H, int W, int Cout, int c0, int c1, int ld0, int ld1, int ldy,
-                                  int has_bias, int has_affine, int stats, int stat_rows, int kwork) {
-  if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || c0 <= 0 || c1 < 0) return S2S_ERR_SHAPE;
-  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+// The plan of the launch s2s_conv3x3_nhwc_s makes of these operands (present or absent; stat_rows as passed to it)
+static Conv3x3Plan conv3x3_query_ep(int dtype, int B, int H, int W, int Cout, int c0, int c1, int ld0, int ld1, int ldy,
+                                    int has_bias, int has_affine, int stats, int stat_rows, int kwork) {
   static float present;
   Conv3x3Args a{};
   conv3x3_fill_args(a, ld0, c0, ld1, c1, has_bias ? &present : nullptr, B, H, W, Cout);
@@ -2625,8 +2624,30 @@ extern "C" int s2s_conv3x3_family(int dtype, int B, int H, int W, int Cout, int 
   a.stat_part = stats ? &present : nullptr;
   a.stat_rows_req = stat_rows;
   a.kpart = kwork ? &present : nullptr;
-  const Conv3x3Plan p = conv3x3_plan(dtype, a);
+  return conv3x3_plan(dtype, a);
+}
+
+extern "C" int s2s_conv3x3_family(int dtype, int B, int H, int W, int Cout, int c0, int c1, int ld0, int ld1, int ldy,
+                                  int has_bias, int has_affine, int stats, int stat_rows, int kwork) {
+  if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || c0 <= 0 || c1 < 0) return S2S_ERR_SHAPE;
+  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  const Conv3x3Plan p = conv3x3_query_ep(dtype, B, H, W, Cout, c0, c1, ld0, ld1, ldy, has_bias, has_affine, stats,
+                                         stat_rows, kwork);
   return p.rc != S2S_OK ? p.rc : p.family;
+}
+
+// out[9] = {family, cfg, gx, gy, grid, xsp, xsn, ksplit, stat_rows} of the same plan
+extern "C" int s2s_conv3x3_plan(int dtype, int B, int H, int W, int Cout, int c0, int c1, int ld0, int ld1, int ldy,
+                                int has_bias, int has_affine, int stats, int stat_rows, int kwork, int* out) {
+  if (!out) return S2S_ERR_NULL;
+  if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || c0 <= 0 || c1 < 0) return S2S_ERR_SHAPE;
+  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  const Conv3x3Plan p = conv3x3_query_ep(dtype, B, H, W, Cout, c0, c1, ld0, ld1, ldy, has_bias, has_affine, stats,
+                                         stat_rows, kwork);
+  if (p.rc != S2S_OK) return p.rc;
+  const int v[9] = {p.family, p.cfg, p.gx, p.gy, p.grid, p.xsp, p.xsn, p.ksplit, (int)p.stat_rows};
+  for (int i = 0; i < 9; ++i) out[i] = v[i];
+  return S2S_OK;
 }
 
 extern "C" int s2s_conv3x3_nhwc_k(int dtype, const void* x0, int ld0, int c0, const void* x1, int ld1, int c1,
@@ -2657,6 +2678,10 @@ extern "C" int s2s_conv3x3_nhwc_s(int dtype, const void* x0, int ld0, int c0, co
   a.ep_scale = ep_scale; a.ep_shift = ep_shift; a.ldy = ldy; a.relu = relu;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  // relu without a folded affine: y = relu(acc + bias) in both modes.  The bf16 epilogues read a.relu inside their
+  // affine branch only, so such a launch takes their activation path (slope 0 = ReLU), which stage_grid() and
+  // pers_eligible() send to the per-tap kernel: its plan is that of the same launch with a bias.
+  if (dtype == S2S_BF16 && relu && !ep_scale) { a.act = 1; a.act_slope = 0.f; }
   a.kpart = kwork;                                     // dispatch() keeps it for a split launch only
   const int rc = dispatch(dtype, a, s);
   if (rc != S2S_OK || !a.kpart) return rc;

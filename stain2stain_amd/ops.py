@@ -342,6 +342,25 @@ def conv3x3(x0: torch.Tensor, x1: Optional[torch.Tensor], w_packed: torch.Tensor
     return out, stat
 
 
+CONV3X3_PLAN_FIELDS = ("family", "cfg", "gx", "gy", "grid", "xsp", "xsn", "ksplit", "stat_rows")
+
+
+def conv3x3_plan(dtype: torch.dtype, B: int, H: int, W: int, c0: int, c1: int, cout: int, *, ld0: Optional[int] = None,
+                 ld1: Optional[int] = None, ldy: Optional[int] = None, bias: bool = False, affine: bool = False,
+                 stats: bool = False, stat_rows: int = -1, kwork: bool = False) -> dict:
+    """What s2s_conv3x3_nhwc_s launches for these operands (s2s_conv3x3_plan): family, tile cfg, pixel x channel tiles,
+    workgroups of the staged / persistent kernels, XCD cut, split count and statistics rows.  stat_rows as handed to the
+    launch (-1: the layout it prefers, 0: one row per tile); kwork: a split-K workspace is offered.  A bf16 launch with
+    relu and no affine has the plan of the same launch with a bias.  Host code only; needs no GPU."""
+    dt = BF16 if dtype == torch.bfloat16 else F32
+    out = (ctypes.c_int * len(CONV3X3_PLAN_FIELDS))()
+    rc = _L().s2s_conv3x3_plan(dt, B, H, W, cout, c0, c1, c0 if ld0 is None else ld0, max(c1, 8) if ld1 is None else ld1,
+                               cout if ldy is None else ldy, int(bias), int(affine), int(stats),
+                               stat_rows if stats else 0, int(kwork), ctypes.cast(out, ctypes.c_void_p))
+    _native.check(rc, "conv3x3_plan")
+    return dict(zip(CONV3X3_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def conv3x3_wgrad(dy: torch.Tensor, x0: torch.Tensor, x1: Optional[torch.Tensor], grad_oihw: torch.Tensor,
                   accumulate: bool = False) -> None:
     B, H, W, cout = dy.shape

@@ -6,7 +6,8 @@ run the convolution parity tests in child processes, so that a non-default path 
   S2S_CONV_STAGE=0 / 2    no launch / every eligible launch on the staged kernel (default 1: filter-resident and
                           single-channel-tile launches)
 (Round 4 deleted what rounds 2-3 had measured and dropped: S2S_WGRAD_KH, S2S_WGRAD_MFMA, S2S_WGRAD_DMA, S2S_CONV_EPI and
-the tuning knobs whose sweeps ended at their defaults; S2S_CONV_DMA and S2S_CONV_CFG followed.)"""
+the tuning knobs whose sweeps ended at their defaults; S2S_CONV_DMA and S2S_CONV_CFG followed.)
+A child takes 46 to 50 s on an MI355X (tests/test_conv3x3_forms_gpu.py is 20 to 25 s of it), well inside its 900 s."""
 import os
 import subprocess
 import sys
@@ -28,6 +29,7 @@ def test_conv_parity_under_switch(env):
                           os.path.join(ROOT, "tests", "test_ops_gpu.py"), os.path.join(ROOT, "tests", "test_fuzz_gpu.py"),
                           os.path.join(ROOT, "tests", "test_unwritten_memory_gpu.py"),
                           os.path.join(ROOT, "tests", "test_wgrad_forms_gpu.py"),
+                          os.path.join(ROOT, "tests", "test_conv3x3_forms_gpu.py"),
                           "-k", "conv3x3 or random_shapes"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env={**os.environ, **env})
     assert out.returncode == 0, out.stdout[-2500:] + out.stderr[-1500:]
