@@ -143,6 +143,10 @@ int s2s_head_conv1x1_bwd(int dtype, const float* dy_nchw, const void* x, int ldx
  * v = W a + b (optional output), loss = mean((v-u)^2), dx = W^T dv, dW/db with dv = 2 (v-u) grad_scale / count
  * (task_decoders.py:132 + conditional_flow_matching.py:72).  part: float[blocks][Cout][C+1]; lpart: double[blocks] */
 int s2s_head_loss_blocks(int B, int H, int W);
+/* test-facing, no launch: the kernel s2s_head_loss_fused takes, from its own dispatch: 1 ... 64 = the lane-per-piece kernel
+ * with that many lanes per pixel (C = 8 lanes, a power of two), 100 = the one-thread-per-pixel kernel (any other
+ * C % 8 == 0 up to 96); a negative status for a launch that is refused (Cout > 4, C % 8, C >= 104 off the lanes form) */
+int s2s_head_loss_family(int dtype, int B, int H, int W, int C, int Cout);
 int s2s_head_loss_fused(int dtype, const void* x, int ldx, const float* w, const float* bias, const float* u_nchw,
                         float* v_nchw, void* dx, int lddx, float grad_scale, float* part, double* lpart, float* dw,
                         float* dbias, float* loss, int accumulate, int B, int H, int W, int C, int Cout, void* stream);
@@ -156,6 +160,9 @@ int s2s_head_loss_fused(int dtype, const void* x, int ldx, const float* w, const
  *   bnwork: float[2*C*nb + 2*C], nb = s2s_bn_bwd_blocks(B, H, W, C)
  * s2s_tail_bwd_apply: dx = d raw (T, NHWC) from raw, g and bnwork. */
 int s2s_tail_blocks(int B, int H, int W);
+/* test-facing, no launch: the instantiation both tail entry points take, from their own dispatch: 256 MO + PCB, PCB = C / 8
+ * lanes per pixel and MO = 3 (Cout <= 3) or 4 outputs covered by the loops; a negative status for a refused launch */
+int s2s_tail_family(int dtype, int B, int H, int W, int C, int Cout);
 int s2s_tail_fwd_loss(int dtype, const void* raw, int ldx, const float* scale, const float* shift, const float* mean,
                       const float* invstd, const float* w, const float* bias, const float* u_nchw, float* v_nchw,
                       float* g_nchw, float grad_scale, float* part, double* lpart, float* bnwork, float* dw,
@@ -430,6 +437,9 @@ int s2s_seg_eval_binary(const float* z, const float* g, float* out, long* counts
 int s2s_seg_eval_multiclass(const float* z, const long* target, float* out, long* counts, double* work, long B,
                             long HW, int C, int ignore_index, float smooth, float dice_weight, void* stream);
 int s2s_head_mse_eval_blocks(int B, int H, int W, int C);
+/* test-facing, no launch: the instantiation s2s_head_mse_eval takes, from its own dispatch: 256 MO + GL, GL = 1, 2, 4, 8
+ * lanes per pixel and MO = 3, 4, 8 outputs unrolled; a negative status for a refused launch */
+int s2s_head_mse_family(int dtype, int B, int H, int W, int C, int Cout);
 int s2s_head_mse_eval(int dtype, const void* x, int ldx, const float* w, const float* bias, const float* u_nchw,
                       float* loss, double* lpart, int B, int H, int W, int C, int Cout, void* stream);
 

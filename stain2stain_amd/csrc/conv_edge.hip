@@ -830,6 +830,22 @@ int head_family(int dtype, int B, int H, int W, int C, int Cout, int forward) {
   return HEAD_FALLBACK + (Cout <= 4 ? 4 : 8);
 }
 
+// Which kernel s2s_head_loss_fused launches (s2s_head_loss_family): the lane-per-piece kernel returns its PCB (C = 8 PCB,
+// PCB a power of two <= 64; static shared memory, a loop over its Cout (C + 1) partial sums), every other C % 8 == 0 the
+// one-thread-per-pixel kernel, HEAD_LOSS_PIXEL, whose limits are its own: a dynamic LDS tile of at most 60 KB (C <= 96)
+// and four partial sums a thread.  A negative status is a launch the entry point refuses; it dispatches on this value.
+constexpr int HEAD_LOSS_PIXEL = 100;
+inline int head_loss_pixel_lds(int C) { return (HEAD_MAX_COUT * C + 256 * HEAD_MAX_COUT) * 4 + 256 * (C + 8) * 2; }
+int head_loss_family(int dtype, int B, int H, int W, int C, int Cout) {
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 8) || Cout <= 0 || Cout > HEAD_MAX_COUT) return S2S_ERR_SHAPE;
+  if ((long)B * H * W >= (1L << 31) - (1L << 20)) return S2S_ERR_SHAPE;   // 32-bit pixel index (+ one grid stride) in the kernels
+  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  const int pcb = C / 8;
+  if (pcb <= 64 && !(pcb & (pcb - 1))) return pcb;
+  if (Cout * (C + 1) > 1024 || head_loss_pixel_lds(C) > 60 * 1024) return S2S_ERR_SHAPE;
+  return HEAD_LOSS_PIXEL;
+}
+
 // launch head_lanes_kernel<T, PP, FWD> for the PP head_family chose
 template <typename T, bool FWD>
 void launch_head_lanes(int pp, const void* x, int ldx, const float* w, const float* bias, const float* dy, float* v, void* dx,
@@ -1260,32 +1276,29 @@ extern "C" int s2s_head_loss_blocks(int B, int H, int W) {
   return (int)(nb < 1024 ? nb : 1024);
 }
 
+extern "C" int s2s_head_loss_family(int dtype, int B, int H, int W, int C, int Cout) {
+  return head_loss_family(dtype, B, H, W, C, Cout);
+}
+
 // part: float[blocks][Cout][C+1]; lpart: double[blocks]; v_out (optional) NCHW fp32; dv scale = 2*grad_scale/count
 extern "C" int s2s_head_loss_fused(int dtype, const void* x, int ldx, const float* w, const float* bias,
                                    const float* u_nchw, float* v_nchw, void* dx, int lddx, float grad_scale,
                                    float* part, double* lpart, float* dw, float* dbias, float* loss, int accumulate,
                                    int B, int H, int W, int C, int Cout, void* stream) {
   if (!x || !w || !u_nchw || !dx || !part || !lpart || !dw || !loss) return S2S_ERR_NULL;
-  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 8) || (ldx % 8) || (lddx % 8) || Cout <= 0 || Cout > HEAD_MAX_COUT)
-    return S2S_ERR_SHAPE;
-  if (Cout * (C + 1) > 1024) return S2S_ERR_SHAPE;
+  if ((ldx % 8) || (lddx % 8)) return S2S_ERR_SHAPE;
+  const int fam = head_loss_family(dtype, B, H, W, C, Cout);
+  if (fam < 0) return fam;
   const long npix = (long)B * H * W;
-  if (npix >= (1L << 31) - (1L << 20)) return S2S_ERR_SHAPE;       // 32-bit pixel index (+ one grid stride) in the kernel
   const double count = (double)npix * Cout;
   const int nb = s2s_head_loss_blocks(B, H, W);
-  const int lds = (HEAD_MAX_COUT * C + 256 * HEAD_MAX_COUT) * 4 + 256 * (C + 8) * 2;
-  if (lds > 60 * 1024) return S2S_ERR_SHAPE;
   hipStream_t s = (hipStream_t)stream;
   const float coef = (float)(2.0 * (double)grad_scale / count);
-  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
-  const int pcb = C / 8;
-  bool done = false;
 #define S2S_HL(TT, PP)                                                                                              \
   hipLaunchKernelGGL((head_loss_lanes_kernel<TT, PP>), dim3(nb), dim3(256), 0, s, (const TT*)x, ldx, w, bias, u_nchw, \
-                     v_nchw, (TT*)dx, lddx, coef, part, lpart, npix, H * W, Cout);                                 \
-  done = true;
+                     v_nchw, (TT*)dx, lddx, coef, part, lpart, npix, H * W, Cout);
 #define S2S_HL_T(TT)                                                                                    \
-  switch (pcb) {                                                                                        \
+  switch (fam) {                                                                                        \
     case 1: { S2S_HL(TT, 1) } break;  case 2: { S2S_HL(TT, 2) } break;  case 4: { S2S_HL(TT, 4) } break;    \
     case 8: { S2S_HL(TT, 8) } break;  case 16: { S2S_HL(TT, 16) } break; case 32: { S2S_HL(TT, 32) } break;  \
     case 64: { S2S_HL(TT, 64) } break; default: break;                                                  \
@@ -1293,7 +1306,8 @@ extern "C" int s2s_head_loss_fused(int dtype, const void* x, int ldx, const floa
   if (dtype == S2S_BF16) { S2S_HL_T(bf16_t) } else { S2S_HL_T(float) }
 #undef S2S_HL_T
 #undef S2S_HL
-  if (!done) {
+  if (fam == HEAD_LOSS_PIXEL) {
+    const int lds = head_loss_pixel_lds(C);
     if (dtype == S2S_BF16)
       hipLaunchKernelGGL(head_loss_fused_kernel<bf16_t>, dim3(nb), dim3(256), lds, s, (const bf16_t*)x, ldx, w, bias,
                          u_nchw, v_nchw, (bf16_t*)dx, lddx, coef, part, lpart, npix, H * W, C, Cout);
@@ -1316,13 +1330,22 @@ int s2s_internal_tail_bn_sums(int dtype, const void* raw, int ldx, const float* 
 extern "C" int s2s_bn_bwd_blocks(int B, int H, int W, int C);
 
 namespace {
-inline bool tail_shape_ok(int B, int H, int W, int C, int Cout, int ldx) {
-  if (B <= 0 || H <= 0 || W <= 0 || C < 8 || (C % 8) || (ldx % 8) || Cout <= 0 || Cout > HEAD_MAX_COUT) return false;
+// Which instantiation a fused-tail launch takes (s2s_tail_family): 256 MO + PCB, PCB = C / 8 lanes per pixel (a power of
+// two <= 64) and MO = 3 or 4 outputs covered by the kernels' loops; a negative status is a launch the entry points
+// refuse.  s2s_tail_fwd_loss and s2s_tail_bwd_apply dispatch on this value.
+int tail_family(int dtype, int B, int H, int W, int C, int Cout) {
+  if (B <= 0 || H <= 0 || W <= 0 || C < 8 || (C % 8) || Cout <= 0 || Cout > HEAD_MAX_COUT) return S2S_ERR_SHAPE;
   const int pcb = C / 8;
-  if (pcb > 64 || (pcb & (pcb - 1))) return false;
-  return (long)B * H * W < (1L << 31) - (1L << 20);      // 32-bit pixel index (+ one grid stride) in the kernels
+  if (pcb > 64 || (pcb & (pcb - 1))) return S2S_ERR_SHAPE;
+  if ((long)B * H * W >= (1L << 31) - (1L << 20)) return S2S_ERR_SHAPE;   // 32-bit pixel index (+ one grid stride) in the kernels
+  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  return 256 * (Cout <= 3 ? 3 : HEAD_MAX_COUT) + pcb;
 }
 }  // namespace
+
+extern "C" int s2s_tail_family(int dtype, int B, int H, int W, int C, int Cout) {
+  return tail_family(dtype, B, H, W, C, Cout);
+}
 
 // workgroups of passes A and B = rows of pass A's partial buffers
 extern "C" int s2s_tail_blocks(int B, int H, int W) { return s2s_head_loss_blocks(B, H, W); }
@@ -1341,22 +1364,23 @@ extern "C" int s2s_tail_fwd_loss(int dtype, const void* raw, int ldx, const floa
   if (!raw || !scale || !shift || !mean || !invstd || !w || !u_nchw || !g_nchw || !part || !lpart || !bnwork || !dw ||
       !loss || !dgamma || !dbeta)
     return S2S_ERR_NULL;
-  if (!tail_shape_ok(B, H, W, C, Cout, ldx)) return S2S_ERR_SHAPE;
-  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  if (ldx % 8) return S2S_ERR_SHAPE;
+  const int fam = tail_family(dtype, B, H, W, C, Cout);
+  if (fam < 0) return fam;
   const long npix = (long)B * H * W;
   const double count = (double)npix * Cout;
   const int nb = s2s_tail_blocks(B, H, W);
   hipStream_t s = (hipStream_t)stream;
   const float coef = (float)(2.0 * (double)grad_scale / count);
 #define S2S_TA(TT, PP)                                                                                               \
-  if (Cout <= 3)                                                                                                     \
+  if (fam >> 8 == 3)                                                                                                 \
     hipLaunchKernelGGL((tail_fwd_loss_kernel<TT, PP, 3>), dim3(nb), dim3(256), 0, s, (const TT*)raw, ldx, scale,     \
                        shift, w, bias, u_nchw, v_nchw, g_nchw, coef, part, lpart, npix, H * W, Cout);                \
   else                                                                                                               \
   hipLaunchKernelGGL((tail_fwd_loss_kernel<TT, PP, HEAD_MAX_COUT>), dim3(nb), dim3(256), 0, s, (const TT*)raw, ldx, scale, shift,   \
                      w, bias, u_nchw, v_nchw, g_nchw, coef, part, lpart, npix, H * W, Cout);
 #define S2S_TA_T(TT)                                                                                    \
-  switch (C / 8) {                                                                                      \
+  switch (fam & 255) {                                                                                  \
     case 1: { S2S_TA(TT, 1) } break;  case 2: { S2S_TA(TT, 2) } break;  case 4: { S2S_TA(TT, 4) } break;    \
     case 8: { S2S_TA(TT, 8) } break;  case 16: { S2S_TA(TT, 16) } break; case 32: { S2S_TA(TT, 32) } break;  \
     default: { S2S_TA(TT, 64) } break;                                                                  \
@@ -1381,21 +1405,22 @@ extern "C" int s2s_tail_bwd_apply(int dtype, const void* raw, int ldx, const flo
                                   const float* gamma, const float* bnwork, void* dx, int lddx, int B, int H, int W,
                                   int C, int Cout, void* stream) {
   if (!raw || !g_nchw || !w || !scale || !shift || !mean || !invstd || !gamma || !bnwork || !dx) return S2S_ERR_NULL;
-  if (!tail_shape_ok(B, H, W, C, Cout, ldx) || (lddx % 8) || lddx < C) return S2S_ERR_SHAPE;
-  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  if ((ldx % 8) || (lddx % 8) || lddx < C) return S2S_ERR_SHAPE;
+  const int fam = tail_family(dtype, B, H, W, C, Cout);
+  if (fam < 0) return fam;
   const long npix = (long)B * H * W;
   const int nb = s2s_tail_blocks(B, H, W);
   const float* const c1 = bnwork + (long)2 * C * s2s_bn_bwd_blocks(B, H, W, C);
   hipStream_t s = (hipStream_t)stream;
 #define S2S_TB(TT, PP)                                                                                              \
-  if (Cout <= 3)                                                                                                    \
+  if (fam >> 8 == 3)                                                                                                \
     hipLaunchKernelGGL((tail_bwd_apply_kernel<TT, PP, 3>), dim3(nb), dim3(256), 0, s, (const TT*)raw, ldx, g_nchw,  \
                        w, scale, shift, mean, invstd, gamma, c1, c1 + C, (TT*)dx, lddx, npix, H * W, Cout);         \
   else                                                                                                              \
   hipLaunchKernelGGL((tail_bwd_apply_kernel<TT, PP, HEAD_MAX_COUT>), dim3(nb), dim3(256), 0, s, (const TT*)raw, ldx, g_nchw, w,    \
                      scale, shift, mean, invstd, gamma, c1, c1 + C, (TT*)dx, lddx, npix, H * W, Cout);
 #define S2S_TB_T(TT)                                                                                    \
-  switch (C / 8) {                                                                                      \
+  switch (fam & 255) {                                                                                  \
     case 1: { S2S_TB(TT, 1) } break;  case 2: { S2S_TB(TT, 2) } break;  case 4: { S2S_TB(TT, 4) } break;    \
     case 8: { S2S_TB(TT, 8) } break;  case 16: { S2S_TB(TT, 16) } break; case 32: { S2S_TB(TT, 32) } break;  \
     default: { S2S_TB(TT, 64) } break;                                                                  \

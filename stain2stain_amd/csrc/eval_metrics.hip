@@ -399,6 +399,16 @@ int head_mse_lanes(int C) {
   return gl;
 }
 
+// Which instantiation s2s_head_mse_eval launches (s2s_head_mse_family): 256 MO + GL, GL = lanes per pixel (1, 2, 4, 8) and
+// MO = 3, 4 or 8 outputs unrolled; a negative status is a launch the entry point refuses.  It dispatches on this value.
+int head_mse_family(int dtype, int B, int H, int W, int C, int Cout) {
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 8) || Cout <= 0 || Cout > 8) return S2S_ERR_SHAPE;
+  if (8 * C * 4 > 60 * 1024) return S2S_ERR_SHAPE;
+  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
+  if ((long)B * H * W >= (1L << 31) - (1L << 22)) return S2S_ERR_SHAPE;   // 32-bit pixel index (+ one grid stride) in the kernel
+  return 256 * (Cout == 3 ? 3 : Cout <= 4 ? 4 : 8) + head_mse_lanes(C);
+}
+
 template <typename T, int MO>
 void head_mse_launch(const void* x, int ldx, const float* w, const float* bias, const float* u, double* lpart, long npix,
                      long HW, int C, int Cout, int gl, int nb, hipStream_t s) {
@@ -453,27 +463,29 @@ extern "C" int s2s_head_mse_eval_blocks(int B, int H, int W, int C) {
   return head_mse_blocks((long)B * H * W, head_mse_lanes(C));
 }
 
+extern "C" int s2s_head_mse_family(int dtype, int B, int H, int W, int C, int Cout) {
+  return head_mse_family(dtype, B, H, W, C, Cout);
+}
+
 extern "C" int s2s_head_mse_eval(int dtype, const void* x, int ldx, const float* w, const float* bias,
                                  const float* u_nchw, float* loss, double* lpart, int B, int H, int W, int C, int Cout,
                                  void* stream) {
   if (!x || !w || !u_nchw || !loss || !lpart) return S2S_ERR_NULL;
-  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C % 8) || ldx < C || (ldx % 8) || Cout <= 0 || Cout > 8)
-    return S2S_ERR_SHAPE;
-  if (8 * C * 4 > 60 * 1024) return S2S_ERR_SHAPE;
+  if (ldx < C || (ldx % 8)) return S2S_ERR_SHAPE;
+  const int fam = head_mse_family(dtype, B, H, W, C, Cout);
+  if (fam < 0) return fam;
   if (((uintptr_t)x) & 15) return S2S_ERR_ALIGN;
-  if (dtype != S2S_BF16 && dtype != S2S_F32) return S2S_ERR_DTYPE;
   const long npix = (long)B * H * W, HW = (long)H * W;
-  if (npix >= (1L << 31) - (1L << 22)) return S2S_ERR_SHAPE;      // 32-bit pixel index (+ one grid stride) in the kernel
-  const int gl = head_mse_lanes(C);
+  const int gl = fam & 255, mo = fam >> 8;
   const int nb = head_mse_blocks(npix, gl);
   hipStream_t s = (hipStream_t)stream;
   if (dtype == S2S_BF16) {
-    if (Cout == 3) head_mse_launch<bf16_t, 3>(x, ldx, w, bias, u_nchw, lpart, npix, HW, C, Cout, gl, nb, s);
-    else if (Cout <= 4) head_mse_launch<bf16_t, 4>(x, ldx, w, bias, u_nchw, lpart, npix, HW, C, Cout, gl, nb, s);
+    if (mo == 3) head_mse_launch<bf16_t, 3>(x, ldx, w, bias, u_nchw, lpart, npix, HW, C, Cout, gl, nb, s);
+    else if (mo == 4) head_mse_launch<bf16_t, 4>(x, ldx, w, bias, u_nchw, lpart, npix, HW, C, Cout, gl, nb, s);
     else head_mse_launch<bf16_t, 8>(x, ldx, w, bias, u_nchw, lpart, npix, HW, C, Cout, gl, nb, s);
   } else {
-    if (Cout == 3) head_mse_launch<float, 3>(x, ldx, w, bias, u_nchw, lpart, npix, HW, C, Cout, gl, nb, s);
-    else if (Cout <= 4) head_mse_launch<float, 4>(x, ldx, w, bias, u_nchw, lpart, npix, HW, C, Cout, gl, nb, s);
+    if (mo == 3) head_mse_launch<float, 3>(x, ldx, w, bias, u_nchw, lpart, npix, HW, C, Cout, gl, nb, s);
+    else if (mo == 4) head_mse_launch<float, 4>(x, ldx, w, bias, u_nchw, lpart, npix, HW, C, Cout, gl, nb, s);
     else head_mse_launch<float, 8>(x, ldx, w, bias, u_nchw, lpart, npix, HW, C, Cout, gl, nb, s);
   }
   hipLaunchKernelGGL(head_mse_finalize_kernel, dim3(1), dim3(256), 0, s, lpart, nb, 1.0 / ((double)npix * Cout), loss);

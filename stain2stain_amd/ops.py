@@ -512,6 +512,29 @@ def head_loss_fused(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tenso
     return loss, dx, v
 
 
+HEAD_LOSS_PIXEL = 100
+
+
+def head_loss_family(dtype: torch.dtype, B: int, H: int, W: int, C: int, cout: int) -> int:
+    """The kernel head_loss_fused takes (s2s_head_loss_family): 1 ... 64 = lanes per pixel of the lane-per-piece kernel,
+    HEAD_LOSS_PIXEL = the one-thread-per-pixel kernel; negative = the launch is refused.  Needs no GPU."""
+    return _L().s2s_head_loss_family(BF16 if dtype == torch.bfloat16 else F32, B, H, W, C, cout)
+
+
+def tail_family(dtype: torch.dtype, B: int, H: int, W: int, C: int, cout: int):
+    """The instantiation tail_fwd_loss / tail_bwd_apply take (s2s_tail_family): (lanes per pixel, outputs their loops
+    cover), or the negative status of a refused launch.  Needs no GPU."""
+    rc = _L().s2s_tail_family(BF16 if dtype == torch.bfloat16 else F32, B, H, W, C, cout)
+    return rc if rc < 0 else (rc & 255, rc >> 8)
+
+
+def head_mse_family(dtype: torch.dtype, B: int, H: int, W: int, C: int, cout: int):
+    """The instantiation head_mse_eval takes (s2s_head_mse_family): (lanes per pixel, outputs unrolled), or the negative
+    status of a refused launch.  Needs no GPU."""
+    rc = _L().s2s_head_mse_family(BF16 if dtype == torch.bfloat16 else F32, B, H, W, C, cout)
+    return rc if rc < 0 else (rc & 255, rc >> 8)
+
+
 def tail_fusable(C: int, cout: int) -> bool:
     """Channel counts the fused tail (tail_fwd_loss / tail_bwd_apply) takes: C = 8 * 2^k <= 512, cout <= 4."""
     pcb = C // 8

@@ -454,7 +454,8 @@ def test_layout_roundtrip_and_error_status():
 @pytest.mark.parametrize("C", [8, 16, 64, 24])
 def test_head_loss_fused_matches_separate_ops(dtype, C):
     """Fused head conv + MSE + backward (training step) against autograd on the CPU.  C = 8, 16, 64 take the
-    lane-per-piece kernel (C/8 a power of two), C = 24 the one-thread-per-pixel form."""
+    lane-per-piece kernel (C/8 a power of two), C = 24 the one-thread-per-pixel form.  (Every form of both kernels against
+    float64: tests/test_head_tail_forms_gpu.py)"""
     from stain2stain_amd import ops
     g = torch.Generator().manual_seed(21)
     B, H, W = 2, 19, 23

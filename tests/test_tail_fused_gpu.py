@@ -11,12 +11,16 @@ Every buffer the ops allocate starts out as NaN (tests/test_unwritten_memory_gpu
 
 Then the trainers: ``fuse_tail`` on and off from the same seed, three optimisation steps, held to the bound
 tests/test_e2e_gpu.py holds the fused trainer to against its golden steps (1e-3 of the loss; 1e-3 of each tensor's
-maximum plus Adam's sign slack of ``slack * lr * steps`` on the parameters).  Three networks, batch 2: features [8, 16] on
+maximum plus Adam's sign slack of ``slack * lr * steps`` on the parameters).  Four networks, batch 2: features [8, 16] on
 32 x 32 tiles; the default first-level width (64 channels into the head, the headline's tail kernels) as [64, 128] on
-16 x 16 tiles; and all five default levels on 16 x 16 tiles.  (The last leaves a 1 x 1 bottleneck whose BatchNorm
+16 x 16 tiles; all five default levels on 16 x 16 tiles; and a first level of 128 channels, [128, 256] on 16 x 16 tiles,
+whose chain head_loss_fused refused until its limits were applied to the one-thread-per-pixel kernel alone.  (The last leaves a 1 x 1 bottleneck whose BatchNorm
 normalises two values per channel: there a one-ulp change of one weight alone moves the third step's loss by 1e-4 of its
 value, and a fused tail that summed in another order than the chain moved it by 1e-2.  It passes because the fused
-results are the chain's bit for bit.)"""
+results are the chain's bit for bit.)
+
+Every form of the tail kernels (all seven widths, both output-loop instantiations, odd and even round counts) against
+float64: tests/test_head_tail_forms_gpu.py, DESIGN.md 3.29."""
 import itertools
 
 import pytest
@@ -192,7 +196,8 @@ def _check_params(got, ref, lr, steps):
         assert err <= TOL * float(r.abs().max()) + slack * lr * steps, (k, err)
 
 
-@pytest.mark.parametrize("features,size", [([8, 16], 32), ([64, 128], 16), (None, 16)], ids=["tiny", "c64", "default16"])
+@pytest.mark.parametrize("features,size", [([8, 16], 32), ([64, 128], 16), (None, 16), ([128, 256], 16)],
+                         ids=["tiny", "c64", "default16", "c128"])
 def test_cfm_trainer_fused_tail_equals_the_chain(features, size):
     from stain2stain_amd import CFMTrainer, FlowUNet, ops
     lr, steps = 1e-4, 3
