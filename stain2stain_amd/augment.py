@@ -31,9 +31,10 @@ import numpy as np
 import torch
 
 from . import _native, ops
+from ._regionio import batch_layout
 from .data import sample_crop_flip_params
 from .stain_norm import _od_floats
-from .stain_quant import _u8_batch, stain_matrix
+from .stain_quant import stain_matrix
 
 _MASK_KINDS = {torch.float32: 1, torch.uint8: 2, torch.int64: 3}
 _PINNED = deque(maxlen=8)      # host tables whose asynchronous copies may still be in flight
@@ -140,14 +141,6 @@ def _check_u8(t, name: str, last: Optional[int], what: str):
         raise ValueError(f"{what}: the pixels of {name} must be contiguous within a row")
 
 
-def _mask_layout(m: torch.Tensor, B: int, H: int, W: int, what: str) -> Tuple[int, int]:
-    pitch = m.stride(1) if H > 1 else W
-    img = m.stride(0) if B > 1 else pitch * H
-    if pitch < W or img < pitch * H:
-        raise ValueError(f"{what}: the rows or samples of mask_u8 overlap")
-    return pitch, img
-
-
 def _check_params(params, B: int, H: int, W: int, size: int, what: str) -> torch.Tensor:
     if not isinstance(params, torch.Tensor):
         raise TypeError(f"{what}: params must be a torch.Tensor, got {type(params).__name__}")
@@ -242,9 +235,9 @@ def paired_augment(src_u8: torch.Tensor, tgt_u8: torch.Tensor, params: torch.Ten
     if tgt_u8.device != dev or (mask_u8 is not None and mask_u8.device != dev):
         raise ValueError(f"{what}: the images are on different devices")
     with torch.no_grad():
-        s, sp, si = _u8_batch(src_u8, B, H, W, what)
-        t, tp, ti = _u8_batch(tgt_u8, B, H, W, what)
-        mp, mi = _mask_layout(mask_u8, B, H, W, what) if mask_u8 is not None else (0, 0)
+        s, sp, si = batch_layout(src_u8, what, "src_u8")
+        t, tp, ti = batch_layout(tgt_u8, what, "tgt_u8")
+        mp, mi = batch_layout(mask_u8, what, "mask_u8")[1:] if mask_u8 is not None else (0, 0)
         keep, p_ptr, sm_ptr, tm_ptr = _upload(dev, params, (src_map, tgt_map))
         out_s = torch.empty((B, 3, size, size), dtype=torch.float32, device=dev)
         out_t = torch.empty_like(out_s)
@@ -276,7 +269,7 @@ def stain_augment(tiles_u8: torch.Tensor, maps: torch.Tensor, *, white: Optional
     maps = _check_map(maps, "maps", B, what)
     white = _check_white(white, what)
     with torch.no_grad():
-        t, pitch, stride = _u8_batch(tiles_u8, B, H, W, what)
+        t, pitch, stride = batch_layout(tiles_u8, what, "tiles_u8")
         keep, _, m_ptr = _upload(t.device, None, (maps,))
         if network_input:
             out = torch.empty((B, 3, H, W), dtype=torch.float32, device=t.device)

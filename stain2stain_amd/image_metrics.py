@@ -24,6 +24,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 import torch
 
 from . import _native, ops
+from ._regionio import BandSource, batch_layout, check_region, gpu_device, gpu_rows
 
 BLOCK_ROWS = 32          # valid rows (and columns) of one workgroup: IQ_TH of csrc/image_metrics.hip
 MAX_WINDOW = 11
@@ -94,10 +95,6 @@ def _check_pair(pred, target, what: str) -> None:
         raise ValueError(f"{what}: pred {list(pred.shape)} and target {list(target.shape)} differ in shape")
 
 
-def _u8_pixels_contiguous(t: torch.Tensor) -> bool:
-    return t.stride(-1) == 1 and (t.shape[-2] == 1 or t.stride(-2) == 3)
-
-
 def _finalize(part: torch.Tensor, B: int, C: int, H: int, W: int, window: int, L: float,
               device) -> Dict[str, torch.Tensor]:
     out = torch.empty((4, B), dtype=torch.float32, device=device)
@@ -141,11 +138,7 @@ def image_quality(pred: torch.Tensor, target: torch.Tensor, *, quantize: bool = 
         raise ValueError("image_quality: empty batch")
     if H < window or W < window:
         raise ValueError(f"image_quality: H and W must be at least the window ({window}), got {H} x {W}")
-    if not pred.is_cuda or not target.is_cuda:
-        raise RuntimeError("stain2stain_amd: image_quality needs GPU tensors (there is no CPU path)")
-    if pred.device != target.device:
-        raise RuntimeError("stain2stain_amd: pred and target are on different devices")
-    part = _partials(pred.device, B, H, W, window)
+    part = _partials(gpu_device("image_quality", pred, target, host_ok=False), B, H, W, window)
     L = ops._L()
     if pred.dtype == torch.float32:
         a, b = pred.detach().contiguous(), target.detach().contiguous()
@@ -153,46 +146,13 @@ def image_quality(pred: torch.Tensor, target: torch.Tensor, *, quantize: bool = 
                                      part.data_ptr(), ops._stream())
         rng = 255.0 if quantize else 1.0
     else:
-        a = pred if _u8_pixels_contiguous(pred) else pred.contiguous()
-        b = target if _u8_pixels_contiguous(target) else target.contiguous()
-        strides = []
-        for t in (a, b):
-            pitch = t.stride(1) if H > 1 else 3 * W
-            img = t.stride(0) if B > 1 else pitch * H
-            if pitch < 3 * W or img < pitch * H:
-                raise ValueError("image_quality: uint8 image rows or samples overlap")
-            strides.append((pitch, img))
-        rc = L.s2s_image_quality_u8(a.data_ptr(), strides[0][0], strides[0][1], b.data_ptr(), strides[1][0],
-                                    strides[1][1], B, 0, H, H, W, 0, -(-(H - window + 1) // BLOCK_ROWS), window, taps,
-                                    k1, k2, part.data_ptr(), ops._stream())
+        (a, pa, ia), (b, pb, ib) = (batch_layout(t, "image_quality", copy=True) for t in (pred, target))
+        rc = L.s2s_image_quality_u8(a.data_ptr(), pa, ia, b.data_ptr(), pb, ib, B, 0, H, H, W, 0,
+                                    -(-(H - window + 1) // BLOCK_ROWS), window, taps, k1, k2, part.data_ptr(),
+                                    ops._stream())
         rng = 255.0
     _native.check(rc, "image_quality")
     return _finalize(part, B, C, H, W, window, rng, pred.device)
-
-
-class _BandSource:
-    """Rows [r0, r1) of a uint8 [H, W, 3] image as a GPU view: the image's own rows when it lives on the GPU, otherwise
-    a band buffer fed through one pinned staging buffer (as ``translate_region`` stages its input)."""
-
-    def __init__(self, img: torch.Tensor, rows: int, device):
-        self.img, self.on_gpu = img, img.is_cuda
-        if not self.on_gpu:
-            W = img.shape[1]
-            self.stage = torch.empty((rows, W, 3), dtype=torch.uint8, pin_memory=True)
-            self.band = torch.empty((rows, W, 3), dtype=torch.uint8, device=device)
-            self.ready = None                     # the GPU's last read of the staging buffer
-
-    def rows(self, r0: int, r1: int) -> torch.Tensor:
-        if self.on_gpu:
-            return self.img[r0:r1]
-        if self.ready is not None:
-            self.ready.synchronize()              # the previous upload has left the staging buffer
-        n = r1 - r0
-        self.stage[:n].copy_(self.img[r0:r1])
-        self.band[:n].copy_(self.stage[:n], non_blocking=True)
-        self.ready = torch.cuda.Event()
-        self.ready.record()
-        return self.band[:n]
 
 
 def region_quality(pred_u8: torch.Tensor, target_u8: torch.Tensor, *, band_rows: Optional[int] = None,
@@ -207,39 +167,30 @@ def region_quality(pred_u8: torch.Tensor, target_u8: torch.Tensor, *, band_rows:
     the block's place in the whole region and summed in a fixed order: the result is bit-equal for every ``band_rows``
     and for host and GPU input.  ``region_quality.last_stats``: bands, band_rows, band_bytes of the last call."""
     _check_pair(pred_u8, target_u8, "region_quality")
-    if pred_u8.dtype != torch.uint8:
-        raise ValueError(f"region_quality: images must be uint8, got {pred_u8.dtype}")
-    if pred_u8.dim() != 3 or pred_u8.shape[2] != 3:
-        raise ValueError(f"region_quality: images must be [H, W, 3] RGB, got {list(pred_u8.shape)}")
-    H, W = int(pred_u8.shape[0]), int(pred_u8.shape[1])
+    H, W, _ = check_region(pred_u8, "region_quality")
+    check_region(target_u8, "region_quality")
     window, taps, k1, k2 = _metric_args(window, sigma, k1, k2)
     if H < window or W < window:
         raise ValueError(f"region_quality: H and W must be at least the window ({window}), got {H} x {W}")
-    for t in (pred_u8, target_u8):
-        if not _u8_pixels_contiguous(t):
-            raise ValueError("region_quality: pixels within a row must be contiguous")
     any_host = not (pred_u8.is_cuda and target_u8.is_cuda)
     if band_rows is None and any_host:
         band_rows = _DEFAULT_HOST_BLOCKS * BLOCK_ROWS + window - 1
     bands = plan_bands(H, window, band_rows)
-    gpu = [t.device for t in (pred_u8, target_u8) if t.is_cuda]
-    if len(gpu) == 2 and gpu[0] != gpu[1]:
-        raise RuntimeError("stain2stain_amd: pred and target are on different devices")
-    dev = gpu[0] if gpu else torch.device("cuda", torch.cuda.current_device())
+    dev = gpu_device("region_quality", pred_u8, target_u8)
     buf_rows = max(r1 - r0 for _, _, r0, r1 in bands)
     with torch.no_grad():
-        src = [_BandSource(t, buf_rows, dev) for t in (pred_u8, target_u8)]
+        src = [BandSource(t, buf_rows, dev) for t in (pred_u8, target_u8)]
         part = _partials(dev, 1, H, W, window)
         L = ops._L()
         for by0, nby, r0, r1 in bands:
             a, b = src[0].rows(r0, r1), src[1].rows(r0, r1)
-            (pa, pitch_a), (pb, pitch_b) = ops._u8_rows(a), ops._u8_rows(b)
+            (pa, pitch_a), (pb, pitch_b) = gpu_rows(a), gpu_rows(b)
             rc = L.s2s_image_quality_u8(pa, pitch_a, pitch_a * (r1 - r0), pb, pitch_b, pitch_b * (r1 - r0), 1, r0,
                                         r1 - r0, H, W, by0, nby, window, taps, k1, k2, part.data_ptr(), ops._stream())
             _native.check(rc, "region_quality")
         out = _finalize(part, 1, 3, H, W, window, 255.0, dev)
     region_quality.last_stats = {"bands": len(bands), "band_rows": buf_rows,
-                                 "band_bytes": sum(0 if s.on_gpu else s.band.numel() for s in src)}
+                                 "band_bytes": sum(s.band_bytes for s in src)}
     return {k: v[0] for k, v in out.items()}
 
 

@@ -31,6 +31,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _native, ops
+from ._regionio import gpu_device
 from .objects import _mask_bytes
 
 FAR = 2 ** 31 - 1            # "no site in this sample" / "beyond max_dist"
@@ -72,15 +73,9 @@ def _squared(value, name: str, what: str) -> int:
 
 def _device(what: str, *masks: torch.Tensor) -> torch.device:
     """The GPU the call runs on: the masks' own, or the current one for host masks (uploaded whole)."""
-    devs = {m.device for m in masks}
-    if len(devs) > 1:
+    if len({m.device for m in masks}) > 1:
         raise RuntimeError(f"stain2stain_amd: {what}: the masks are on different devices")
-    dev = devs.pop()
-    if dev.type == "cuda":
-        return dev
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"stain2stain_amd: {what} needs a GPU (there is no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device())
+    return gpu_device(what, *masks)
 
 
 def _scratch(dev, words: int, what: str) -> torch.Tensor:

@@ -33,12 +33,11 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import _native, ops
-from .image_metrics import _BandSource
+from ._regionio import DEFAULT_HOST_BAND, BandSource, batch_layout, check_region, gpu_device, gpu_rows
 from .morphology import FAR, MAX_SIDE, distance_transform
 from .objects import (_FG_POSITIVE, _check_mpp, _density, _label, _object_args, _stain_dict, _stain_mask)
 from .region import _check_thresholds
-from .stain_quant import (DEFAULT_THRESHOLDS, _DEFAULT_HOST_BAND, _check_region, _image_kind, _kernel_args, _need_gpu,
-                          _stain_index, _u8_batch, plan_stain_bands)
+from .stain_quant import DEFAULT_THRESHOLDS, _image_kind, _kernel_args, _stain_index, plan_stain_bands
 
 TILE = (64, 64)              # rows x columns of the shape pass's workgroup tile: OF_TH, OF_TW of csrc/object_features.hip
 LDS_SLOTS = 64               # labels a workgroup gathers in LDS before it falls back to global atomics: OF_SLOTS
@@ -124,7 +123,7 @@ def _intensity_pass(labels: torch.Tensor, image: torch.Tensor, kind: str, t: Dic
                                          t["sum_q"].data_ptr(), t["sum_q2"].data_ptr(), t["max_q"].data_ptr(),
                                          ops._stream())
     else:
-        a, pitch, stride = _u8_batch(image, B, H, W, what)
+        a, pitch, stride = batch_layout(image, what, copy=True)
         rc = L.s2s_objfeat_intensity_u8(labels.data_ptr(), a.data_ptr(), pitch, stride, B, 0, H, H, W, M, table, unmix,
                                         stain, t["sum_q"].data_ptr(), t["sum_q2"].data_ptr(), t["max_q"].data_ptr(),
                                         ops._stream())
@@ -219,7 +218,7 @@ def object_features(labels: torch.Tensor, max_objects: int = 256, image: Optiona
         image, kind = _check_image(image, labels, B, H, W, what)
         stain = _stain_index(stain)
         table, unmix = _kernel_args(stains, DEFAULT_THRESHOLDS)
-    dev = _need_gpu(what, labels, *([image] if image is not None else []))
+    dev = gpu_device(what, labels, *([image] if image is not None else []), host_ok=False)
     with torch.no_grad():
         lab = labels.detach()
         lab = (lab if lab.dim() == 3 else lab[None]).contiguous()
@@ -247,7 +246,7 @@ def stain_object_features(img: torch.Tensor, max_objects: int = 256, stain: int 
     white, black = _check_thresholds(white, black)
     connectivity, min_area, _ = _object_args(connectivity, min_area, None, what)
     mpp = _check_mpp(mpp, what)
-    dev = _need_gpu(what, img)
+    dev = gpu_device(what, img, host_ok=False)
     with torch.no_grad():
         mask, tissue = _stain_mask(img, kind, B, H, W, table, unmix, white, black, stain, what)
         res = _label(mask.data_ptr(), W, H * W, _FG_POSITIVE, B, H, W, dev, connectivity, min_area, 0, what)
@@ -268,7 +267,7 @@ def region_stain_object_features(region_u8: torch.Tensor, max_objects: int = 409
     band by band through the same band source, its integer sums accumulating across the bands, so a host region never
     sits on the GPU as RGB.  The result is bit-equal for every ``band_rows`` and for host and GPU input."""
     what = "region_stain_object_features"
-    H, W = _check_region(region_u8, what)
+    H, W, _ = check_region(region_u8, what)
     _check_sides(H, W, what)
     M = _check_max_objects(max_objects, 1, what)
     stain = _stain_index(stain)
@@ -277,18 +276,16 @@ def region_stain_object_features(region_u8: torch.Tensor, max_objects: int = 409
     connectivity, min_area, _ = _object_args(connectivity, min_area, None, what)
     mpp = _check_mpp(mpp, what)
     if band_rows is None and not region_u8.is_cuda:
-        band_rows = _DEFAULT_HOST_BAND
+        band_rows = DEFAULT_HOST_BAND
     bands = plan_stain_bands(H, H, band_rows)
-    if not region_u8.is_cuda and not torch.cuda.is_available():
-        raise RuntimeError(f"stain2stain_amd: {what} needs a GPU (there is no CPU path)")
-    dev = region_u8.device if region_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = gpu_device(what, region_u8)
     with torch.no_grad():
-        src = _BandSource(region_u8, max(r1 - r0 for _, _, r0, r1 in bands), dev)
+        src = BandSource(region_u8, max(r1 - r0 for _, _, r0, r1 in bands), dev)
         mask = torch.empty((1, H, W), dtype=torch.uint8, device=dev)
         tissue = torch.zeros((1,), dtype=torch.int64, device=dev)
         L = ops._L()
         for _, _, r0, r1 in bands:
-            ptr, pitch = ops._u8_rows(src.rows(r0, r1))
+            ptr, pitch = gpu_rows(src.rows(r0, r1))
             rc = L.s2s_stain_mask_u8(ptr, pitch, pitch * (r1 - r0), 1, r0, r1 - r0, H, W, table, unmix, white, black,
                                      stain, mask.data_ptr(), W, H * W, tissue.data_ptr(), ops._stream())
             _native.check(rc, what)
@@ -300,7 +297,7 @@ def region_stain_object_features(region_u8: torch.Tensor, max_objects: int = 409
         d2 = distance_transform(labels > 0, to="background") if thickness else None
         _shape_pass(labels, d2, t, 1, H, W, M, what)
         for _, _, r0, r1 in bands:
-            ptr, pitch = ops._u8_rows(src.rows(r0, r1))
+            ptr, pitch = gpu_rows(src.rows(r0, r1))
             rc = L.s2s_objfeat_intensity_u8(labels.data_ptr(), ptr, pitch, pitch * (r1 - r0), 1, r0, r1 - r0, H, W, M,
                                             table, unmix, stain, t["sum_q"].data_ptr(), t["sum_q2"].data_ptr(),
                                             t["max_q"].data_ptr(), ops._stream())

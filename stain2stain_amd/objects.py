@@ -31,10 +31,10 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import _native, ops
-from .image_metrics import _BandSource, _check_pair
+from ._regionio import DEFAULT_HOST_BAND, BandSource, batch_layout, check_region, gpu_device, gpu_rows
+from .image_metrics import _check_pair
 from .region import _check_thresholds
-from .stain_quant import (DEFAULT_THRESHOLDS, _DEFAULT_HOST_BAND, _check_region, _image_kind, _kernel_args, _need_gpu,
-                          _stain_index, _u8_batch, plan_stain_bands)
+from .stain_quant import DEFAULT_THRESHOLDS, _image_kind, _kernel_args, _stain_index, plan_stain_bands
 
 TILE = (32, 64)                    # rows x columns of the local pass's tile: OT_H, OT_W of csrc/objects.hip
 MAX_PIXELS = 2 ** 31 - 2           # per sample: parents are int32 raster indices
@@ -155,7 +155,7 @@ def label_components(mask: torch.Tensor, *, connectivity: int = 8, min_area: int
     bit-reproducible; a sample's values do not depend on its batch mates; no host synchronisation."""
     B, H, W = _check_mask(mask, "label_components")
     connectivity, min_area, M = _object_args(connectivity, min_area, max_objects, "label_components")
-    dev = _need_gpu("label_components", mask)
+    dev = gpu_device("label_components", mask, host_ok=False)
     with torch.no_grad():
         m, pitch, img = _mask_bytes(mask, B, H, W)
         res = _label(m.data_ptr(), pitch, img, _FG_ANY, B, H, W, dev, connectivity, min_area, M, "label_components")
@@ -174,7 +174,7 @@ def _stain_mask(img: torch.Tensor, kind: str, B: int, H: int, W: int, table, unm
         rc = L.s2s_stain_mask_f32(a.data_ptr(), B, H, W, table, unmix, white, black, stain, mask.data_ptr(), W, H * W,
                                   tissue.data_ptr(), ops._stream())
     else:
-        a, pitch, stride = _u8_batch(img, B, H, W, what)
+        a, pitch, stride = batch_layout(img, what, copy=True)
         rc = L.s2s_stain_mask_u8(a.data_ptr(), pitch, stride, B, 0, H, H, W, table, unmix, white, black, stain,
                                  mask.data_ptr(), W, H * W, tissue.data_ptr(), ops._stream())
     _native.check(rc, what)
@@ -229,7 +229,7 @@ def stain_objects(img: torch.Tensor, *, stain: int = 1, stains="hdab",
     white, black = _check_thresholds(white, black)
     connectivity, min_area, M = _object_args(connectivity, min_area, max_objects, "stain_objects")
     mpp = _check_mpp(mpp, "stain_objects")
-    dev = _need_gpu("stain_objects", img)
+    dev = gpu_device("stain_objects", img, host_ok=False)
     with torch.no_grad():
         mask, tissue = _stain_mask(img, kind, B, H, W, table, unmix, white, black, stain, "stain_objects")
         res = _label(mask.data_ptr(), W, H * W, _FG_POSITIVE, B, H, W, dev, connectivity, min_area, M, "stain_objects")
@@ -252,7 +252,7 @@ def stain_object_agreement(pred: torch.Tensor, target: torch.Tensor, *, stain: i
     table, unmix = _kernel_args(stains, thresholds)
     white, black = _check_thresholds(white, black)
     connectivity, min_area, _ = _object_args(connectivity, min_area, None, "stain_object_agreement")
-    dev = _need_gpu("stain_object_agreement", pred, target)
+    dev = gpu_device("stain_object_agreement", pred, target, host_ok=False)
     what = "stain_object_agreement"
     with torch.no_grad():
         res = []
@@ -286,7 +286,7 @@ def region_stain_objects(region_u8: torch.Tensor, *, band_rows: Optional[int] = 
     labels).  The result is bit-equal for every ``band_rows`` and for host and GPU input.  Raises ``ValueError`` when
     ``H * W`` exceeds ``MAX_PIXELS`` = 2^31 - 2."""
     what = "region_stain_objects"
-    H, W = _check_region(region_u8, what)
+    H, W, _ = check_region(region_u8, what)
     _check_pixels(H, W, what)
     stain = _stain_index(stain)
     table, unmix = _kernel_args(stains, thresholds)
@@ -294,16 +294,16 @@ def region_stain_objects(region_u8: torch.Tensor, *, band_rows: Optional[int] = 
     connectivity, min_area, M = _object_args(connectivity, min_area, max_objects, what)
     mpp = _check_mpp(mpp, what)
     if band_rows is None and not region_u8.is_cuda:
-        band_rows = _DEFAULT_HOST_BAND
+        band_rows = DEFAULT_HOST_BAND
     bands = plan_stain_bands(H, H, band_rows)
-    dev = region_u8.device if region_u8.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = gpu_device(what, region_u8)
     with torch.no_grad():
-        src = _BandSource(region_u8, max(r1 - r0 for _, _, r0, r1 in bands), dev)
+        src = BandSource(region_u8, max(r1 - r0 for _, _, r0, r1 in bands), dev)
         mask = torch.empty((1, H, W), dtype=torch.uint8, device=dev)
         tissue = torch.zeros((1,), dtype=torch.int64, device=dev)
         L = ops._L()
         for _, _, r0, r1 in bands:
-            ptr, pitch = ops._u8_rows(src.rows(r0, r1))
+            ptr, pitch = gpu_rows(src.rows(r0, r1))
             rc = L.s2s_stain_mask_u8(ptr, pitch, pitch * (r1 - r0), 1, r0, r1 - r0, H, W, table, unmix, white, black,
                                      stain, mask.data_ptr(), W, H * W, tissue.data_ptr(), ops._stream())
             _native.check(rc, what)

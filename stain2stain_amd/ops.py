@@ -17,6 +17,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _native
+from ._regionio import gpu_rows
 
 BF16, F32 = 0, 1
 
@@ -2019,26 +2020,11 @@ def convsm_wins(dtype: torch.dtype, mode: int, B: int, h: int, w: int, cin: int,
 # ------------------------------------------------------------------------------------------------
 # tiled whole-region translation (region.hip; the driver is region.translate_region)
 # ------------------------------------------------------------------------------------------------
-def _u8_rows(img: torch.Tensor) -> Tuple[int, int]:
-    """(data_ptr, row pitch in bytes) of a uint8 [rows, W, 3] GPU view whose pixels are contiguous within a row."""
-    if not img.is_cuda:
-        raise RuntimeError("stain2stain_amd: tensor is not on the GPU (there is no CPU path)")
-    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
-        raise RuntimeError("stain2stain_amd: expected a uint8 [rows, W, 3] image")
-    rows, w, _ = img.shape
-    if img.stride(2) != 1 or (w > 1 and img.stride(1) != 3):
-        raise RuntimeError("stain2stain_amd: image pixels must be contiguous within a row")
-    pitch = img.stride(0) if rows > 1 else 3 * w
-    if pitch < 3 * w:
-        raise RuntimeError("stain2stain_amd: image rows overlap")
-    return img.data_ptr(), pitch
-
-
 def region_gather(band: torch.Tensor, band_top: int, H: int, W: int, origins: torch.Tensor, tile: int,
                   out: torch.Tensor) -> torch.Tensor:
     """out[n] = Normalize(0.5, 0.5)(to_tensor(tile at origins[n])), fp32 [B, 3, tile, tile]: ``band`` holds image rows
     [band_top, band_top + band.shape[0]) of an H x W uint8 RGB image; pixels outside the image fold back by reflection."""
-    ptr, pitch = _u8_rows(band)
+    ptr, pitch = gpu_rows(band)
     B = origins.shape[0]
     if (origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 2 or not origins.is_cuda
             or not origins.is_contiguous()):
@@ -2075,7 +2061,7 @@ def region_finalize(acc: torch.Tensor, r0: int, r1: int, out_u8: Optional[torch.
     band_rows, W, C1 = acc.shape
     pu8, pitch_u8, pf, pitch_f = 0, 0, 0, 0
     if out_u8 is not None:
-        pu8, pitch_u8 = _u8_rows(out_u8)
+        pu8, pitch_u8 = gpu_rows(out_u8)
         if out_u8.shape[1] != W or out_u8.shape[0] < r1 - out_top:
             raise RuntimeError("stain2stain_amd: region_finalize uint8 output too small")
     if out_f is not None:
@@ -2093,7 +2079,7 @@ def region_tissue_count(band: torch.Tensor, band_top: int, H: int, W: int, origi
     """counts[k] = the pixels of tile k's intersection with the H x W image for which min(R, G, B) < white and
     max(R, G, B) >= black (int32 [n], every entry written); ``band`` as in ``region_gather``.  A tile whose in-image
     rows are not all inside the band gets -1."""
-    ptr, pitch = _u8_rows(band)
+    ptr, pitch = gpu_rows(band)
     n = origins.shape[0]
     if (origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 2 or not origins.is_cuda
             or not origins.is_contiguous()):
@@ -2132,12 +2118,12 @@ def region_finalize_mixed(acc: torch.Tensor, ws: torch.Tensor, r0: int, r1: int,
     band_rows, W, C1 = acc.shape
     if tuple(ws.shape) != (band_rows, W) or not ws.is_contiguous():
         raise RuntimeError("stain2stain_amd: region_finalize_mixed weight ring shape mismatch")
-    psrc, src_pitch = _u8_rows(src)
+    psrc, src_pitch = gpu_rows(src)
     if src.shape[1] != W or src_top > r0 or src.shape[0] < r1 - src_top:
         raise RuntimeError("stain2stain_amd: region_finalize_mixed source rows do not cover [r0, r1)")
     pu8, pitch_u8, pf, pitch_f = 0, 0, 0, 0
     if out_u8 is not None:
-        pu8, pitch_u8 = _u8_rows(out_u8)
+        pu8, pitch_u8 = gpu_rows(out_u8)
         if out_u8.shape[1] != W or out_u8.shape[0] < r1 - out_top:
             raise RuntimeError("stain2stain_amd: region_finalize_mixed uint8 output too small")
     if out_f is not None:

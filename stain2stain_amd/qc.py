@@ -37,9 +37,9 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _native, ops
-from .image_metrics import _BandSource
+from ._regionio import DEFAULT_HOST_BAND, BandSource, batch_layout, check_region, gpu_device, gpu_rows
 from .region import _axis_origins, _check_thresholds, plan_tiles
-from .stain_quant import _check_cell, _check_region, _u8_batch
+from .stain_quant import _check_cell
 
 CHUNK_ROWS = 16                    # rows of one wave's chunk: QC_CH of csrc/qc.hip
 COUNT_KEYS = ("tissue", "focus_n", "lap_sum", "lap_sq", "luma_sum", "green", "blue", "dark")
@@ -48,7 +48,6 @@ DERIVED_KEYS = ("focus", "tissue_frac", "ink_frac", "dark_frac", "mean_luma")
 # fold or a speck of dust is darker than stained tissue.  Calibrate on your own slides.
 DEFAULT_INK_CHROMA = 40
 DEFAULT_DARK = 60
-_DEFAULT_HOST_BAND = 512           # band rows of a host region when band_rows is not given
 
 
 def _check_qc_thresholds(white, black, ink_chroma, dark) -> Tuple[int, int, int, int]:
@@ -98,7 +97,7 @@ def tile_qc(tiles_u8: torch.Tensor, *, white: int = 220, black: int = 0, ink_chr
         raise RuntimeError(f"stain2stain_amd: {what} needs GPU tensors (there is no CPU path)")
     dev = tiles_u8.device
     with torch.no_grad():
-        t, pitch, stride = _u8_batch(tiles_u8, B, H, W, what)
+        t, pitch, stride = batch_layout(tiles_u8, what, copy=True)
         nchunk = _chunks(H, W)
         origins = torch.zeros((1, 2), dtype=torch.int32, device=dev)
         slab = ops._workspace(dev, 2 * B * nchunk * 8, "qc").view(torch.int64)
@@ -130,12 +129,10 @@ def _reduce_windows(region: torch.Tensor, H: int, W: int, plan: torch.Tensor, nx
     """counts and derived values of the ``win_h x win_w`` windows at ``plan``, host int32 ``[ny * nx, 2]`` = (top, left),
     a row-major grid whose tops do not decrease.  The origins are uploaded once from pinned memory; a band's launch
     covers only the window rows it touches, and the finalize adds into their counts."""
-    if not region.is_cuda and not torch.cuda.is_available():
-        raise RuntimeError(f"stain2stain_amd: {what} needs a GPU (there is no CPU path)")
+    dev = gpu_device(what, region)
     if band_rows is None and not region.is_cuda:
-        band_rows = _DEFAULT_HOST_BAND
+        band_rows = DEFAULT_HOST_BAND
     bands = plan_qc_bands(H, band_rows)
-    dev = region.device if region.is_cuda else torch.device("cuda", torch.cuda.current_device())
     N = int(plan.shape[0])
     tops = plan[::nx, 0].tolist()
     nchunk = _chunks(win_h, win_w)
@@ -144,7 +141,7 @@ def _reduce_windows(region: torch.Tensor, H: int, W: int, plan: torch.Tensor, nx
         host = torch.empty((N, 2), dtype=torch.int32, pin_memory=True)
         host.copy_(plan)
         origins = host.to(dev, non_blocking=True)            # the one upload; a band's windows are a slice
-        src = _BandSource(region, buf_rows, dev)
+        src = BandSource(region, buf_rows, dev)
         # a band adds into the counts of the windows it touches, and leaves the fp64 values of the counts so far
         counts = torch.zeros((N, 8), dtype=torch.int64, device=dev)
         derived = torch.empty((N, len(DERIVED_KEYS)), dtype=torch.float64, device=dev)
@@ -154,7 +151,7 @@ def _reduce_windows(region: torch.Tensor, H: int, W: int, plan: torch.Tensor, nx
                 continue
             p0, n = i0 * nx, (i1 - i0) * nx
             b0, b1 = max(r0 - 1, 0), min(r1 + 1, H)
-            ptr, pitch = ops._u8_rows(src.rows(b0, b1))
+            ptr, pitch = gpu_rows(src.rows(b0, b1))
             slab = ops._workspace(dev, 2 * n * nchunk * 8, "qc").view(torch.int64)
             _native.check(ops._L().s2s_qc_windows_u8(ptr, pitch, pitch * (b1 - b0), 1, b0, b1 - b0, H, W,
                                                      origins[p0:p0 + n].data_ptr(), n, win_h, win_w, r0, r1, *thr,
@@ -163,7 +160,7 @@ def _reduce_windows(region: torch.Tensor, H: int, W: int, plan: torch.Tensor, nx
                       derived[p0:p0 + n], what)
         res = _result(counts, derived)
     stats_of.last_stats = {"bands": len(bands), "band_rows": buf_rows, "windows": N,
-                           "band_bytes": 0 if src.on_gpu else src.band.numel()}
+                           "band_bytes": src.band_bytes}
     return res
 
 
@@ -179,7 +176,7 @@ def region_qc(region_u8: torch.Tensor, tile: int = 256, overlap: int = 32, *, ba
     ``band_rows`` rows (any number from 1 on; default 512) plus a row of halo on either side.  The counts are bit-equal
     for host and GPU input and for every ``band_rows``.  ``region_qc.last_stats``: bands, band_rows, windows, band_bytes
     of the last call.  Thresholds as ``tile_qc``."""
-    H, W = _check_region(region_u8, "region_qc")
+    H, W, _ = check_region(region_u8, "region_qc")
     plan = plan_tiles(H, W, tile, overlap)
     thr = _check_qc_thresholds(white, black, ink_chroma, dark)
     tile = operator.index(tile)
@@ -198,7 +195,7 @@ def region_qc_map(region_u8: torch.Tensor, cell: int = 256, *, band_rows: Option
     The cells tile the region, so their counts add up exactly to those of the whole region, and ``window_sums`` turns
     the map into the counts of any window of whole cells.  Input, banding and bit equality as ``region_qc``;
     ``region_qc_map.last_stats`` likewise."""
-    H, W = _check_region(region_u8, "region_qc_map")
+    H, W, _ = check_region(region_u8, "region_qc_map")
     cell = _check_cell(cell)
     thr = _check_qc_thresholds(white, black, ink_chroma, dark)
     Gy, Gx = -(-H // cell), -(-W // cell)

@@ -18,6 +18,7 @@ from typing import Callable, Dict, List, Optional
 import torch
 
 from . import ops
+from ._regionio import BandSink, BandSource, check_region, gpu_device
 
 
 def _axis_origins(L: int, tile: int, overlap: int) -> List[int]:
@@ -107,136 +108,135 @@ def translate_region(image: torch.Tensor, sampler: Callable, *, tile: int = 256,
     where kept and skipped tiles overlap, the skipped ones enter the blend as the normalised source, so there are no
     seams.  The output channels must then be known before the first sampler call: ``mask_channels`` is the sampler's
     number of probability channels (default: its ``mask_channels`` attribute, which ``multitask_sampler`` sets, else 0)."""
-    if not isinstance(image, torch.Tensor):
-        raise TypeError(f"translate_region: image must be a torch.Tensor, got {type(image).__name__}")
-    if image.dtype != torch.uint8:
-        raise ValueError(f"translate_region: image must be uint8, got {image.dtype}")
-    if image.dim() != 3 or image.shape[2] != 3:
-        raise ValueError(f"translate_region: image must be [H, W, 3] RGB, got {list(image.shape)}")
-    H, W = int(image.shape[0]), int(image.shape[1])
-    if image.stride(2) != 1 or (W > 1 and image.stride(1) != 3):
-        raise ValueError("translate_region: pixels within a row must be contiguous")
+    H, W, _ = check_region(image, "translate_region")
     batch = operator.index(batch)
     if batch < 1:
         raise ValueError(f"batch must be >= 1, got {batch}")
     plan = plan_tiles(H, W, tile, overlap)
     if tile % 4:
         raise ValueError(f"tile must be a multiple of 4, got {tile}")
-    if min_tissue is not None or keep is not None:
-        return _translate_skipping(image, sampler, plan, tile, overlap, batch, return_float, min_tissue, keep, white,
-                                   black, mask_channels)
-    on_gpu = image.is_cuda
-    dev = image.device if on_gpu else torch.device("cuda", torch.cuda.current_device())
+    skipping = min_tissue is not None or keep is not None
+    C = None                                              # output channels: the first sampler call tells
+    if skipping:
+        if min_tissue is not None and keep is not None:
+            raise ValueError("translate_region: keep and min_tissue exclude each other")
+        white, black = _check_thresholds(white, black)
+        if min_tissue is not None:
+            min_tissue = float(min_tissue)
+            if not 0.0 <= min_tissue <= 1.0:
+                raise ValueError(f"translate_region: min_tissue must lie in [0, 1], got {min_tissue}")
+        if mask_channels is None:
+            mask_channels = getattr(sampler, "mask_channels", 0)
+        C = 3 + operator.index(mask_channels)             # a range without kept tiles is finalised before any call
+        if not 3 <= C <= 8:
+            raise ValueError(f"translate_region: mask_channels must lie in 0..5, got {C - 3}")
     N = plan.shape[0]
-    nb = -(-N // batch)
-    padded = torch.cat([plan, plan[-1:].expand(nb * batch - N, 2)]) if nb * batch > N else plan
-    tops = plan[:, 0].tolist()
-    origins = padded.to(dev)                              # one upload; a batch is a slice
+    on_gpu = image.is_cuda
+    dev = gpu_device("translate_region", image)
     band_rows = band_rows_for(H, W, tile, overlap, batch)
-    x = torch.empty((batch, 3, tile, tile), dtype=torch.float32, device=dev)
-    if not on_gpu:
-        stage_in = torch.empty((band_rows, W, 3), dtype=torch.uint8, pin_memory=True)
-        band_in = torch.empty((band_rows, W, 3), dtype=torch.uint8, device=dev)
-        in_ready = None                                   # the GPU's last read of stage_in
-    acc = out_u8 = out_f = None
-    C = Cm = 0
-    fin = 0                                               # rows [0, fin) are final
-    pending = None                                        # host output rows in flight: (event, r0, r1)
-
-    def drain():                                          # host image: staged output rows -> the result
-        ev, a, b = pending
-        ev.synchronize()
-        res_u8[a:b] = stage_u8[:b - a]
-        if res_f is not None:
-            res_f[a:b] = stage_f[:b - a]
-
-    for bi in range(nb):
-        p0, pn = bi * batch, min(batch, N - bi * batch)
-        r0, r1 = tops[p0], min(H, tops[p0 + pn - 1] + tile)
+    source = BandSource(image, band_rows, dev)
+    tops = plan[:, 0].tolist()
+    if min_tissue is not None:
+        counts = _count_tissue(source, plan, plan.to(dev), tile, white, black, dev).tolist()
+        if min(counts) < 0:                               # .tolist(): the one host synchronisation skipping adds
+            raise RuntimeError("translate_region: a tile was counted outside its band")
+        keep = torch.tensor([c >= min_tissue * a for c, a in zip(counts, _tile_areas(plan, H, W, tile).tolist())],
+                            dtype=torch.bool)
+    elif isinstance(keep, torch.Tensor):
+        keep = keep.cpu()
+    if skipping:
+        ranges = plan_region_batches(plan, keep, batch, band_rows, tile)
+        kept = keep.tolist()
+    else:
+        ranges = [(p0, min(p0 + batch, N)) for p0 in range(0, N, batch)]
+        kept = [True] * N
+    # one upload: per range its kept origins, padded to `batch` by repeating the last one, then its skipped origins
+    rows, layout = [], []
+    for p0, p1 in ranges:
+        ks = [p for p in range(p0, p1) if kept[p]]
+        ss = [p for p in range(p0, p1) if not kept[p]]
+        ko = len(rows)
+        if ks:
+            rows += ks + [ks[-1]] * (batch - len(ks))
+        layout.append((len(ks), len(ss), ko, len(rows)))
+        rows += ss
+    origins = plan[rows].contiguous().to(dev)
+    n_kept = sum(kept)
+    x = torch.empty((batch, 3, tile, tile), dtype=torch.float32, device=dev) if n_kept else None
+    ws = torch.zeros((band_rows, W), dtype=torch.float32, device=dev) if skipping else None
+    acc = out_u8 = out_f = sink = None
+    if C is not None:
+        acc, out_u8, out_f, sink = _result_buffers(H, W, C, band_rows, return_float, on_gpu, dev)
+    fin = 0                                               # rows [0, fin) are final; fin is the range's first top
+    calls = 0
+    for (p0, p1), (nk, ns, ko, so) in zip(ranges, layout):
+        r0, r1 = tops[p0], min(H, tops[p1 - 1] + tile)
+        done = tops[p1] if p1 < N else H                  # no later tile covers rows above the next range's first top
         if on_gpu:
-            ops.region_gather(image, 0, H, W, origins[p0:p0 + batch], tile, x)
+            src, src_top = image, 0
         else:
-            if in_ready is not None:
-                in_ready.synchronize()                    # the previous upload has left stage_in
-            stage_in[:r1 - r0].copy_(image[r0:r1])
-            band_in[:r1 - r0].copy_(stage_in[:r1 - r0], non_blocking=True)
-            in_ready = torch.cuda.Event()
-            in_ready.record()
-            ops.region_gather(band_in[:r1 - r0], r0, H, W, origins[p0:p0 + batch], tile, x)
-        out = sampler(x)
-        probs = None
-        if isinstance(out, tuple):
-            if len(out) != 2:
-                raise ValueError(f"translate_region: a tuple from the sampler must be (image, probabilities), "
-                                 f"got {len(out)} items")
-            out, probs = out
-            probs = _check_output(probs, batch, tile, dev, "probabilities", channels=5)
-        out = _check_output(out, batch, tile, dev, "image")
-        c_now = 3 + (0 if probs is None else probs.shape[1])
-        if acc is None:
-            C, Cm = c_now, c_now - 3
-            acc = torch.zeros((band_rows, W, C + 1), dtype=torch.float32, device=dev)
-            want_f = return_float or Cm > 0
-            if on_gpu:
-                res_u8 = out_u8 = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
-                res_f = out_f = torch.empty((H, W, C), dtype=torch.float32, device=dev) if want_f else None
-            else:
-                res_u8 = torch.empty((H, W, 3), dtype=torch.uint8)
-                res_f = torch.empty((H, W, C), dtype=torch.float32) if want_f else None
-                out_u8 = torch.empty((band_rows, W, 3), dtype=torch.uint8, device=dev)
-                out_f = torch.empty((band_rows, W, C), dtype=torch.float32, device=dev) if want_f else None
-                stage_u8 = torch.empty((band_rows, W, 3), dtype=torch.uint8, pin_memory=True)
-                stage_f = torch.empty((band_rows, W, C), dtype=torch.float32, pin_memory=True) if want_f else None
-        elif c_now != C:
-            raise ValueError("translate_region: the sampler changed its output channels between calls")
-        ops.region_blend(out[:pn], None if probs is None else probs[:pn], origins[p0:p0 + pn], overlap, acc,
-                         band_rows, H, W, r0, r1)
-        done = tops[p0 + pn] if bi + 1 < nb else H        # no later tile covers rows above the next tile's top
+            rs = r1 if nk else done                       # without kept tiles only the rows to finalise are read
+            src, src_top = source.rows(r0, rs) if rs > r0 else None, r0
+        if ns:
+            ops.region_skip_weight(origins[so:so + ns], tile, overlap, ws, H, r0, r1)
+        if nk:
+            ops.region_gather(src, src_top, H, W, origins[ko:ko + batch], tile, x)
+            out = sampler(x)
+            calls += 1
+            probs = None
+            if isinstance(out, tuple):
+                if len(out) != 2:
+                    raise ValueError(f"translate_region: a tuple from the sampler must be (image, probabilities), "
+                                     f"got {len(out)} items")
+                out, probs = out
+                probs = _check_output(probs, batch, tile, dev, "probabilities", channels=5)
+            out = _check_output(out, batch, tile, dev, "image")
+            c_now = 3 + (0 if probs is None else probs.shape[1])
+            if acc is None:
+                C = c_now
+                acc, out_u8, out_f, sink = _result_buffers(H, W, C, band_rows, return_float, on_gpu, dev)
+            elif c_now != C:
+                raise ValueError(f"translate_region: the sampler changed its output channels: {C - 3} probability "
+                                 f"channels were expected (mask_channels, or its first call), it returned {c_now - 3}")
+            ops.region_blend(out[:nk], None if probs is None else probs[:nk], origins[ko:ko + nk], overlap, acc,
+                             band_rows, H, W, r0, r1)
         if done > fin:
-            if on_gpu:
-                ops.region_finalize(acc, fin, done, out_u8, out_f, 0)
+            out_top = 0 if on_gpu else fin                # a host result leaves through the band buffers' first rows
+            if skipping:
+                ops.region_finalize_mixed(acc, ws, fin, done, src, src_top, out_u8, out_f, out_top)
             else:
-                ops.region_finalize(acc, fin, done, out_u8, out_f, fin)
-                if pending is not None:
-                    drain()                               # stage_u8 / stage_f are free again
-                n = done - fin
-                stage_u8[:n].copy_(out_u8[:n], non_blocking=True)
-                if out_f is not None:
-                    stage_f[:n].copy_(out_f[:n], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                pending = (ev, fin, done)
+                ops.region_finalize(acc, fin, done, out_u8, out_f, out_top)
+            if sink is not None:
+                sink.put(out_u8, fin, done, out_f)
             fin = done
-    if pending is not None:
-        drain()
-    translate_region.last_stats = {"tiles": N, "batches": nb, "band_rows": band_rows,
-                                   "accumulator_bytes": acc.numel() * acc.element_size(), "channels": C,
-                                   "kept": N, "skipped": 0, "sampler_calls": nb}
+    res_u8, res_f = (out_u8, out_f) if on_gpu else sink.close()
+    translate_region.last_stats = {"tiles": N, "batches": len(ranges), "band_rows": band_rows,
+                                   "accumulator_bytes": (acc.numel() + (ws.numel() if skipping else 0)) * 4,
+                                   "channels": C, "kept": n_kept, "skipped": N - n_kept, "sampler_calls": calls}
     extra = []
-    if Cm:
+    if C > 3:
         extra.append(res_f[..., 3:])
     if return_float:
         extra.append(res_f[..., :3])
     return (res_u8, *extra) if extra else res_u8
 
 
+def _result_buffers(H: int, W: int, C: int, band_rows: int, return_float: bool, on_gpu: bool, dev):
+    """(accumulator ring, uint8 and fp32 rows the finalize writes, sink): for a GPU image the rows are the whole result
+    and there is no sink; for a host image they are band buffers that a ``BandSink`` empties."""
+    acc = torch.zeros((band_rows, W, C + 1), dtype=torch.float32, device=dev)
+    want_f = return_float or C > 3
+    rows = H if on_gpu else band_rows
+    out_u8 = torch.empty((rows, W, 3), dtype=torch.uint8, device=dev)
+    out_f = torch.empty((rows, W, C), dtype=torch.float32, device=dev) if want_f else None
+    sink = None if on_gpu else BandSink((H, W, 3), band_rows, C if want_f else None)
+    return acc, out_u8, out_f, sink
+
+
 translate_region.last_stats: Optional[Dict[str, int]] = None
 
 
 # ---- tissue-aware regions: background tiles skip the sampler (DESIGN.md section 3.16) --------------------------------
-def _check_image(image, who: str):
-    if not isinstance(image, torch.Tensor):
-        raise TypeError(f"{who}: image must be a torch.Tensor, got {type(image).__name__}")
-    if image.dtype != torch.uint8:
-        raise ValueError(f"{who}: image must be uint8, got {image.dtype}")
-    if image.dim() != 3 or image.shape[2] != 3:
-        raise ValueError(f"{who}: image must be [H, W, 3] RGB, got {list(image.shape)}")
-    H, W = int(image.shape[0]), int(image.shape[1])
-    if image.stride(2) != 1 or (W > 1 and image.stride(1) != 3):
-        raise ValueError(f"{who}: pixels within a row must be contiguous")
-    return H, W
-
-
 def _check_thresholds(white, black):
     white, black = operator.index(white), operator.index(black)
     if not 1 <= white <= 256:
@@ -246,36 +246,24 @@ def _check_thresholds(white, black):
     return white, black
 
 
-def _count_tissue(image, plan, origins, tile, white, black, dev, stage_in=None, band_in=None):
-    """int32 [N] tissue counts on the GPU.  A GPU image takes one launch; a host image streams once through the pinned
-    buffer ``stage_in`` and its GPU twin ``band_in`` (at least min(H, tile) rows each), one tile row of the plan per band."""
-    H, W = int(image.shape[0]), int(image.shape[1])
+def _count_tissue(source: BandSource, plan, origins, tile, white, black, dev):
+    """int32 [N] tissue counts on the GPU.  A GPU image takes one launch; a host image streams once through ``source``
+    (at least min(H, tile) rows), one tile row of the plan per band."""
+    H, W = int(source.img.shape[0]), int(source.img.shape[1])
     N = plan.shape[0]
     counts = torch.empty((N,), dtype=torch.int32, device=dev)
-    if image.is_cuda:
-        ops.region_tissue_count(image, 0, H, W, origins[:N], tile, white, black, counts)
+    if source.on_gpu:
+        ops.region_tissue_count(source.img, 0, H, W, origins[:N], tile, white, black, counts)
         return counts
-    rows = min(H, tile)
-    if stage_in is None:
-        stage_in = torch.empty((rows, W, 3), dtype=torch.uint8, pin_memory=True)
-        band_in = torch.empty((rows, W, 3), dtype=torch.uint8, device=dev)
     tops = plan[:, 0].tolist()
-    in_ready = None
     p0 = 0
     while p0 < N:
         p1 = p0 + 1
         while p1 < N and tops[p1] == tops[p0]:
             p1 += 1
         r0, r1 = tops[p0], min(H, tops[p0] + tile)
-        if in_ready is not None:
-            in_ready.synchronize()                        # the previous upload has left stage_in
-        stage_in[:r1 - r0].copy_(image[r0:r1])
-        band_in[:r1 - r0].copy_(stage_in[:r1 - r0], non_blocking=True)
-        in_ready = torch.cuda.Event()
-        in_ready.record()
-        ops.region_tissue_count(band_in[:r1 - r0], r0, H, W, origins[p0:p1], tile, white, black, counts[p0:p1])
+        ops.region_tissue_count(source.rows(r0, r1), r0, H, W, origins[p0:p1], tile, white, black, counts[p0:p1])
         p0 = p1
-    in_ready.synchronize()                                # stage_in is the caller's again
     return counts
 
 
@@ -290,11 +278,12 @@ def tissue_counts(image: torch.Tensor, tile: int = 256, overlap: int = 32, *, wh
     1..256, ``black`` in 0..255, 0 disabling the dark test.  A tile's area is its intersection with the image: the
     reflected padding of a region smaller than a tile is not counted.  ``image`` as for ``translate_region``; a host
     image is streamed once through a pinned buffer, one tile row of the plan per band."""
-    H, W = _check_image(image, "tissue_counts")
+    H, W, _ = check_region(image, "tissue_counts")
     white, black = _check_thresholds(white, black)
     plan = plan_tiles(H, W, tile, overlap)
-    dev = image.device if image.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    return _count_tissue(image, plan, plan.to(dev), tile, white, black, dev), _tile_areas(plan, H, W, tile)
+    dev = gpu_device("tissue_counts", image)
+    source = BandSource(image, min(H, operator.index(tile)), dev)
+    return _count_tissue(source, plan, plan.to(dev), tile, white, black, dev), _tile_areas(plan, H, W, tile)
 
 
 def plan_region_batches(plan: torch.Tensor, keep: torch.Tensor, batch: int, band_rows: int, tile: int):
@@ -330,145 +319,6 @@ def plan_region_batches(plan: torch.Tensor, keep: torch.Tensor, batch: int, band
         ranges.append((p0, p1))
         p0 = p1
     return ranges
-
-
-def _translate_skipping(image, sampler, plan, tile, overlap, batch, return_float, min_tissue, keep, white, black,
-                        mask_channels):
-    """``translate_region`` with ``min_tissue`` or ``keep``: per range of ``plan_region_batches``, the skipped tiles'
-    window weights go to a second ring, the kept tiles are gathered compacted (padded to ``batch``), sampled and blended,
-    and the rows above the next range's first top are finalised against the source (``s2s_region_finalize_mixed``)."""
-    if min_tissue is not None and keep is not None:
-        raise ValueError("translate_region: keep and min_tissue exclude each other")
-    white, black = _check_thresholds(white, black)
-    if min_tissue is not None:
-        min_tissue = float(min_tissue)
-        if not 0.0 <= min_tissue <= 1.0:
-            raise ValueError(f"translate_region: min_tissue must lie in [0, 1], got {min_tissue}")
-    if mask_channels is None:
-        mask_channels = getattr(sampler, "mask_channels", 0)
-    Cm = operator.index(mask_channels)
-    if not 0 <= Cm <= 5:
-        raise ValueError(f"translate_region: mask_channels must lie in 0..5, got {Cm}")
-    C = 3 + Cm
-    H, W = int(image.shape[0]), int(image.shape[1])
-    N = plan.shape[0]
-    on_gpu = image.is_cuda
-    dev = image.device if on_gpu else torch.device("cuda", torch.cuda.current_device())
-    band_rows = band_rows_for(H, W, tile, overlap, batch)
-    if not on_gpu:
-        stage_in = torch.empty((band_rows, W, 3), dtype=torch.uint8, pin_memory=True)
-        band_in = torch.empty((band_rows, W, 3), dtype=torch.uint8, device=dev)
-        in_ready = None                                   # the GPU's last read of stage_in
-    if min_tissue is not None:
-        counts = _count_tissue(image, plan, plan.to(dev), tile, white, black, dev,
-                               *(() if on_gpu else (stage_in, band_in)))
-        counts = counts.tolist()                          # the one host synchronisation skipping adds
-        if min(counts) < 0:
-            raise RuntimeError("translate_region: a tile was counted outside its band")
-        keep = torch.tensor([c >= min_tissue * a for c, a in zip(counts, _tile_areas(plan, H, W, tile).tolist())],
-                            dtype=torch.bool)
-    elif isinstance(keep, torch.Tensor):
-        keep = keep.cpu()
-    ranges = plan_region_batches(plan, keep, batch, band_rows, tile)
-    kept = keep.tolist()
-    # one upload: per range its kept origins, padded to `batch` by repeating the last one, then its skipped origins
-    rows, layout = [], []
-    for p0, p1 in ranges:
-        ks = [p for p in range(p0, p1) if kept[p]]
-        ss = [p for p in range(p0, p1) if not kept[p]]
-        ko = len(rows)
-        if ks:
-            rows += ks + [ks[-1]] * (batch - len(ks))
-        layout.append((len(ks), len(ss), ko, len(rows)))
-        rows += ss
-    origins = plan[rows].contiguous().to(dev)
-    tops = plan[:, 0].tolist()
-    n_kept = sum(kept)
-    x = torch.empty((batch, 3, tile, tile), dtype=torch.float32, device=dev) if n_kept else None
-    acc = torch.zeros((band_rows, W, C + 1), dtype=torch.float32, device=dev)
-    ws = torch.zeros((band_rows, W), dtype=torch.float32, device=dev)
-    want_f = return_float or Cm > 0
-    if on_gpu:
-        res_u8 = out_u8 = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
-        res_f = out_f = torch.empty((H, W, C), dtype=torch.float32, device=dev) if want_f else None
-    else:
-        res_u8 = torch.empty((H, W, 3), dtype=torch.uint8)
-        res_f = torch.empty((H, W, C), dtype=torch.float32) if want_f else None
-        out_u8 = torch.empty((band_rows, W, 3), dtype=torch.uint8, device=dev)
-        out_f = torch.empty((band_rows, W, C), dtype=torch.float32, device=dev) if want_f else None
-        stage_u8 = torch.empty((band_rows, W, 3), dtype=torch.uint8, pin_memory=True)
-        stage_f = torch.empty((band_rows, W, C), dtype=torch.float32, pin_memory=True) if want_f else None
-    fin = 0                                               # rows [0, fin) are final; fin is the range's first top
-    calls = 0
-    pending = None                                        # host output rows in flight: (event, r0, r1)
-
-    def drain():                                          # host image: staged output rows -> the result
-        ev, a, b = pending
-        ev.synchronize()
-        res_u8[a:b] = stage_u8[:b - a]
-        if res_f is not None:
-            res_f[a:b] = stage_f[:b - a]
-
-    for (p0, p1), (nk, ns, ko, so) in zip(ranges, layout):
-        r0, r1 = tops[p0], min(H, tops[p1 - 1] + tile)
-        done = tops[p1] if p1 < N else H                  # no later tile covers rows above the next range's first top
-        if on_gpu:
-            src, src_top = image, 0
-        else:
-            rs = r1 if nk else done                       # without kept tiles only the rows to finalise are read
-            if rs > r0:
-                if in_ready is not None:
-                    in_ready.synchronize()                # the previous upload has left stage_in
-                stage_in[:rs - r0].copy_(image[r0:rs])
-                band_in[:rs - r0].copy_(stage_in[:rs - r0], non_blocking=True)
-                in_ready = torch.cuda.Event()
-                in_ready.record()
-            src, src_top = band_in[:max(rs - r0, 1)], r0
-        if ns:
-            ops.region_skip_weight(origins[so:so + ns], tile, overlap, ws, H, r0, r1)
-        if nk:
-            ops.region_gather(src, src_top, H, W, origins[ko:ko + batch], tile, x)
-            out = sampler(x)
-            calls += 1
-            probs = None
-            if isinstance(out, tuple):
-                if len(out) != 2:
-                    raise ValueError(f"translate_region: a tuple from the sampler must be (image, probabilities), "
-                                     f"got {len(out)} items")
-                out, probs = out
-                probs = _check_output(probs, batch, tile, dev, "probabilities", channels=5)
-            out = _check_output(out, batch, tile, dev, "image")
-            if 3 + (0 if probs is None else probs.shape[1]) != C:
-                raise ValueError(f"translate_region: the sampler changed its output channels: mask_channels says "
-                                 f"{Cm} probability channels, it returned {0 if probs is None else probs.shape[1]}")
-            ops.region_blend(out[:nk], None if probs is None else probs[:nk], origins[ko:ko + nk], overlap, acc,
-                             band_rows, H, W, r0, r1)
-        if done > fin:
-            if on_gpu:
-                ops.region_finalize_mixed(acc, ws, fin, done, src, src_top, out_u8, out_f, 0)
-            else:
-                ops.region_finalize_mixed(acc, ws, fin, done, src, src_top, out_u8, out_f, fin)
-                if pending is not None:
-                    drain()                               # stage_u8 / stage_f are free again
-                n = done - fin
-                stage_u8[:n].copy_(out_u8[:n], non_blocking=True)
-                if out_f is not None:
-                    stage_f[:n].copy_(out_f[:n], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                pending = (ev, fin, done)
-            fin = done
-    if pending is not None:
-        drain()
-    translate_region.last_stats = {"tiles": N, "batches": len(ranges), "band_rows": band_rows,
-                                   "accumulator_bytes": (acc.numel() + ws.numel()) * acc.element_size(),
-                                   "channels": C, "kept": n_kept, "skipped": N - n_kept, "sampler_calls": calls}
-    extra = []
-    if Cm:
-        extra.append(res_f[..., 3:])
-    if return_float:
-        extra.append(res_f[..., :3])
-    return (res_u8, *extra) if extra else res_u8
 
 
 def multitask_sampler(module, num_steps: int, graph: bool = True, *, method: str = "euler", atol: float = 1e-4,

@@ -34,9 +34,10 @@ from typing import Dict, Optional
 import torch
 
 from . import _native, ops
-from .image_metrics import _BandSource, image_quality
+from ._regionio import BandSource, batch_layout, check_region, gpu_device, gpu_rows
+from .image_metrics import image_quality
 from .stain_norm import q_table
-from .stain_quant import _check_region, _det, _stain_index, stain_matrix
+from .stain_quant import _det, _stain_index, stain_matrix
 
 MAX_RADIUS = 32              # RG_MAX_R of csrc/registration.hip
 MAX_TEMPLATE = 1 << 18       # template pixels at the centre 0: n * sum(a b) stays below 2^53
@@ -91,17 +92,10 @@ def _u8_layout(t, name: str, what: str, channels: Optional[int] = 3):
         raise ValueError(f"{what}: {name} must be uint8 {shape}, got {t.dtype}")
     if t.dim() != (4 if channels else 3) or (channels and t.shape[3] != channels) or min(t.shape) < 1:
         raise ValueError(f"{what}: {name} must be a non-empty uint8 {shape}, got {list(t.shape)}")
-    B, H, W = (int(v) for v in t.shape[:3])
-    c = channels or 1
-    if (channels and t.stride(3) != 1) or (W > 1 and t.stride(2) != c):
-        raise ValueError(f"{what}: the pixels of {name} must be contiguous within a row")
+    _, pitch, img = batch_layout(t, what, name, interleave=True)
     if not t.is_cuda:
         raise ValueError(f"{what}: {name} must be on the GPU (there is no CPU path)")
-    pitch = t.stride(1) if H > 1 else c * W
-    img = t.stride(0) if B > 1 else pitch * H
-    if pitch < c * W or img < 1:
-        raise ValueError(f"{what}: the rows of {name} overlap")
-    return B, H, W, pitch, img
+    return (*(int(v) for v in t.shape[:3]), pitch, img)
 
 
 def _as_u8(t, name: str, what: str) -> torch.Tensor:
@@ -352,8 +346,8 @@ def region_shift_field(src_region_u8: torch.Tensor, tgt_region_u8: torch.Tensor,
     uploaded one cell row at a time through a pinned buffer, which waits for the previous upload.  ``register_kwargs``
     as ``register_pairs`` (no ``center``, no ``return_surface``)."""
     what = "region_shift_field"
-    H, W = _check_region(src_region_u8, what)
-    if _check_region(tgt_region_u8, what) != (H, W):
+    H, W, _ = check_region(src_region_u8, what)
+    if check_region(tgt_region_u8, what) != (H, W, 3):
         raise ValueError(f"{what}: the regions differ in shape")
     cell = operator.index(cell)
     if cell < 1 or cell > H or cell > W:
@@ -361,22 +355,17 @@ def region_shift_field(src_region_u8: torch.Tensor, tgt_region_u8: torch.Tensor,
     for k in ("center", "return_surface"):
         if k in register_kwargs:
             raise ValueError(f"{what}: {k} is not available here")
-    gpu = [t.device for t in (src_region_u8, tgt_region_u8) if t.is_cuda]
-    if len(gpu) == 2 and gpu[0] != gpu[1]:
-        raise ValueError(f"{what}: the regions are on different devices")
-    if not gpu and not torch.cuda.is_available():
-        raise RuntimeError(f"stain2stain_amd: {what} needs a GPU (there is no CPU path)")
-    dev = gpu[0] if gpu else torch.device("cuda", torch.cuda.current_device())
+    dev = gpu_device(what, src_region_u8, tgt_region_u8, mismatch=ValueError)
     Gy, Gx = H // cell, W // cell
     keys = ("shift", "score", "margin", "valid")
     rows = {k: [] for k in keys}
     with torch.no_grad():
-        src = [_BandSource(t, cell, dev) for t in (src_region_u8, tgt_region_u8)]
+        src = [BandSource(t, cell, dev) for t in (src_region_u8, tgt_region_u8)]
         for gy in range(Gy):
             views = []
             for s in src:
                 band = s.rows(gy * cell, (gy + 1) * cell)
-                pitch = band.stride(0) if cell > 1 else 3 * W
+                pitch = gpu_rows(band)[1]
                 views.append(band.as_strided((Gx, cell, cell, 3), (3 * cell, pitch, 3, 1)))
             out = register_pairs(views[0], views[1], **register_kwargs)
             for k in keys:

@@ -38,11 +38,12 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import _native, ops
+from ._regionio import gpu_device
 from .morphology import MAX_SIDE, _check_mask, _squared, distance_transform
 from .objects import (_FG_POSITIVE, _check_mpp, _check_pixels, _density, _label, _object_args, _scratch, _stain_dict,
                       _stain_mask, _words)
 from .region import _check_thresholds
-from .stain_quant import DEFAULT_THRESHOLDS, _image_kind, _kernel_args, _need_gpu, _stain_index
+from .stain_quant import DEFAULT_THRESHOLDS, _image_kind, _kernel_args, _stain_index
 
 TILE = (32, 64)                    # rows x columns of the ascent pass's tile: ST_H, ST_W of csrc/split.hip
 NECK_ONE = 1024                    # the neck ratio is compared in 1/1024
@@ -129,7 +130,7 @@ def split_objects(mask: torch.Tensor, *, neck: float = 0.75, min_core: float = 0
     connectivity, min_area, M = _object_args(connectivity, min_area, max_objects, what)
     if d2 is not None:
         d2 = _check_d2(d2, mask, what)
-    dev = _need_gpu(what, mask)
+    dev = gpu_device(what, mask, host_ok=False)
     with torch.no_grad():
         if d2 is None:
             d2 = distance_transform(mask)
@@ -161,7 +162,7 @@ def stain_object_split(img: torch.Tensor, *, stain: int = 1, stains="hdab",
     neck_q, core2 = _split_args(neck, min_core, what)
     connectivity, min_area, M = _object_args(connectivity, min_area, max_objects, what)
     mpp = _check_mpp(mpp, what)
-    dev = _need_gpu(what, img)
+    dev = gpu_device(what, img, host_ok=False)
     with torch.no_grad():
         mask, tissue = _stain_mask(img, kind, B, H, W, table, unmix, white, black, stain, what)
         positive = mask & _FG_POSITIVE
@@ -202,7 +203,7 @@ def label_agreement(labels_pred: torch.Tensor, count_pred: torch.Tensor, labels_
     if _check_labels(labels_target, count_target, "target", what) != (B, H, W) or labels_pred.dim() != labels_target.dim():
         raise ValueError(f"{what}: labels_pred {list(labels_pred.shape)} and labels_target {list(labels_target.shape)} "
                          f"differ in shape")
-    dev = _need_gpu(what, labels_pred, count_pred, labels_target, count_target)
+    dev = gpu_device(what, labels_pred, count_pred, labels_target, count_target, host_ok=False)
     with torch.no_grad():
         lp, lt = labels_pred.detach().contiguous(), labels_target.detach().contiguous()
         cp, ct = count_pred.detach().contiguous().view(B), count_target.detach().contiguous().view(B)

@@ -40,8 +40,8 @@ from typing import Callable, List, Optional, Tuple
 import torch
 
 from . import _native, ops
-from .image_metrics import _BandSource
-from .stain_quant import _check_region, _u8_batch, od_table, unmix_matrix
+from ._regionio import DEFAULT_HOST_BAND, BandSink, BandSource, batch_layout, check_region, gpu_device, gpu_rows
+from .stain_quant import od_table, unmix_matrix
 
 NB = 4096                # histogram bins: SN_NB of csrc/stain_norm.hip
 CONC_MAX = 4.0           # the concentration histograms cover [0, CONC_MAX) in log10 OD
@@ -49,7 +49,6 @@ MOMENT_BITS = 12         # q(u) = rint(od(u) * 2^MOMENT_BITS)
 MIN_PIXELS = 16          # fewer kept pixels than this is no OD cloud to fit
 CHUNK_ROWS = 16          # rows of one workgroup's chunk in pass A: SN_CH of csrc/stain_norm.hip
 _MAX_BAND = CHUNK_ROWS * 65535     # (grid.y)
-_DEFAULT_HOST_BAND = 512           # band rows of a host region when band_rows is not given
 _DEGENERATE = 1e-12      # a second eigenvalue below this share of the first is rounding noise of a one-stain cloud
 
 
@@ -163,8 +162,7 @@ def _check_image(img, what: str) -> Tuple[int, int, int]:
     if not isinstance(img, torch.Tensor):
         raise TypeError(f"{what}: the image must be a torch.Tensor, got {type(img).__name__}")
     if img.dim() == 3:
-        H, W = _check_region(img, what)
-        return 1, H, W
+        return (1,) + check_region(img, what)[:2]
     if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3 or min(img.shape[:3]) < 1:
         raise ValueError(f"{what}: expected a non-empty uint8 [H, W, 3] or [B, H, W, 3] image, got {img.dtype} "
                          f"{list(img.shape)}")
@@ -176,7 +174,7 @@ def _check_image(img, what: str) -> Tuple[int, int, int]:
 def _bands(H: int, band_rows: Optional[int], on_gpu: bool) -> List[Tuple[int, int]]:
     """[r0, r1) row ranges: whole chunk rows of pass A, at most ``band_rows`` rows each."""
     if band_rows is None:
-        band_rows = _MAX_BAND if on_gpu else _DEFAULT_HOST_BAND
+        band_rows = _MAX_BAND if on_gpu else DEFAULT_HOST_BAND
     band_rows = operator.index(band_rows)
     if band_rows < CHUNK_ROWS:
         raise ValueError(f"band_rows must be at least {CHUNK_ROWS}, got {band_rows}")
@@ -184,27 +182,19 @@ def _bands(H: int, band_rows: Optional[int], on_gpu: bool) -> List[Tuple[int, in
     return [(r0, min(r0 + step, H)) for r0 in range(0, H, step)]
 
 
-def _device_of(img: torch.Tensor) -> torch.device:
-    if img.is_cuda:
-        return img.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("stain2stain_amd: stain normalisation needs a GPU (there is no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _each_band(img: torch.Tensor, band_rows, what: str, launch: Callable) -> None:
     """``launch(ptr, pitch, img_stride, B, r0, rows, H, W, first)`` for every band of ``img``, in order."""
     B, H, W = _check_image(img, what)
     if img.dim() == 4:
-        t, pitch, stride = _u8_batch(img, B, H, W, what)
+        t, pitch, stride = batch_layout(img, what, copy=True)
         if H > _MAX_BAND:
             raise ValueError(f"{what}: a batch image has at most {_MAX_BAND} rows")
         _native.check(launch(t.data_ptr(), pitch, stride, B, 0, H, H, W, True), what)
         return
     bands = _bands(H, band_rows, img.is_cuda)
-    src = _BandSource(img, max(r1 - r0 for r0, r1 in bands), _device_of(img))
+    src = BandSource(img, max(r1 - r0 for r0, r1 in bands), gpu_device(what, img))
     for i, (r0, r1) in enumerate(bands):
-        ptr, pitch = ops._u8_rows(src.rows(r0, r1))
+        ptr, pitch = gpu_rows(src.rows(r0, r1))
         _native.check(launch(ptr, pitch, pitch * (r1 - r0), 1, r0, r1 - r0, H, W, i == 0), what)
 
 
@@ -225,7 +215,7 @@ def moments(img_u8: torch.Tensor, *, beta: float = 0.15, black: int = 0,
     over the kept pixels of a uint8 ``[H, W, 3]`` image (GPU or host) or a ``[B, H, W, 3]`` GPU batch (pooled)."""
     B, H, W = _check_image(img_u8, "stain moments")
     ub, black = u_beta(beta), _check_black(black)
-    dev = _device_of(img_u8)
+    dev = gpu_device("stain moments", img_u8)
     L = ops._L()
     slots = L.s2s_stain_moments_slots(B, H, W)
     _native.check(slots if slots < 0 else 0, "stain_moments_slots")
@@ -250,7 +240,7 @@ def angle_histogram(img_u8: torch.Tensor, plane: torch.Tensor, *, beta: float = 
     if tuple(plane.shape) != (3, 2) or not torch.isfinite(plane).all():
         raise ValueError(f"plane must be a finite [3, 2] array, got {list(plane.shape)}")
     ub, black = u_beta(beta), _check_black(black)
-    dev = _device_of(img_u8)
+    dev = gpu_device("stain angle histogram", img_u8)
     L = ops._L()
     table, coef = _od_floats(), _c_floats(plane.reshape(-1).tolist())
     with torch.no_grad():
@@ -269,7 +259,7 @@ def concentration_histogram(img_u8: torch.Tensor, vectors, *, beta: float = 0.15
     _check_image(img_u8, "stain concentration histogram")
     ub, black = u_beta(beta), _check_black(black)
     table, coef = _od_floats(), _c_floats(unmix_matrix(vectors).reshape(-1).tolist())
-    dev = _device_of(img_u8)
+    dev = gpu_device("stain concentration histogram", img_u8)
     L = ops._L()
     with torch.no_grad():
         hist = torch.empty((2, NB), dtype=torch.int64, device=dev)
@@ -347,7 +337,7 @@ def stain_normalize(tiles_u8: torch.Tensor, fit: Optional[StainFit] = None, *, r
         fit = fit_stains(tiles_u8)
     table, coef = _apply_args(fit, reference)
     with torch.no_grad():
-        t, pitch, stride = _u8_batch(tiles_u8, B, H, W, "stain_normalize")
+        t, pitch, stride = batch_layout(tiles_u8, "stain_normalize", copy=True)
         if network_input:
             out = torch.empty((B, 3, H, W), dtype=torch.float32, device=t.device)
         else:
@@ -364,31 +354,27 @@ def normalize_region(region_u8: torch.Tensor, fit: Optional[StainFit] = None, *,
     device.  A GPU region is one launch.  A host region is staged in and out through pinned bands of ``band_rows`` rows
     (``None``: 512), so GPU memory does not grow with H; the bytes do not depend on the banding.  ``fit=None`` fits on
     the region itself first."""
-    H, W = _check_region(region_u8, "normalize_region")
+    H, W, _ = check_region(region_u8, "normalize_region")
     if fit is None:
         fit = fit_stains(region_u8, band_rows=band_rows)
     table, coef = _apply_args(fit, reference)
     bands = _bands(H, band_rows, region_u8.is_cuda)
-    dev = _device_of(region_u8)
+    dev = gpu_device("normalize_region", region_u8)
     L = ops._L()
     with torch.no_grad():
         if region_u8.is_cuda:
             out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
-            ptr, pitch = ops._u8_rows(region_u8)
+            ptr, pitch = gpu_rows(region_u8)
             _native.check(L.s2s_stain_normalize_u8(ptr, pitch, pitch * H, 1, H, W, table, coef, out.data_ptr(), 3 * W,
                                                    3 * W * H, 0, ops._stream()), "normalize_region")
             return out
         rows = max(r1 - r0 for r0, r1 in bands)
-        src = _BandSource(region_u8, rows, dev)
+        src, sink = BandSource(region_u8, rows, dev), BandSink((H, W, 3), rows)
         band = torch.empty((rows, W, 3), dtype=torch.uint8, device=dev)
-        stage = torch.empty((rows, W, 3), dtype=torch.uint8, pin_memory=True)
-        out = torch.empty((H, W, 3), dtype=torch.uint8)
         for r0, r1 in bands:
             n = r1 - r0
-            ptr, pitch = ops._u8_rows(src.rows(r0, r1))
+            ptr, pitch = gpu_rows(src.rows(r0, r1))
             _native.check(L.s2s_stain_normalize_u8(ptr, pitch, pitch * n, 1, n, W, table, coef, band.data_ptr(), 3 * W,
                                                    3 * W * n, 0, ops._stream()), "normalize_region")
-            stage[:n].copy_(band[:n], non_blocking=True)
-            torch.cuda.current_stream().synchronize()     # the band has landed in the staging buffer
-            out[r0:r1].copy_(stage[:n])
-    return out
+            sink.put(band, r0, r1)
+        return sink.close()[0]

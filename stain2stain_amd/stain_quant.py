@@ -31,14 +31,14 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _native, ops
-from .image_metrics import _BandSource, _check_pair, _u8_pixels_contiguous
+from ._regionio import DEFAULT_HOST_BAND, BandSource, batch_layout, check_region, gpu_device, gpu_rows
+from .image_metrics import _check_pair
 from .region import _check_thresholds
 
 CHUNK_ROWS = 16          # rows of one workgroup's chunk: SQ_CH of csrc/stain_quant.hip
 # A convention, not a calibration: 0.2 OD is a common starting point for "DAB positive" in open-source pathology tools.
 # The right value depends on the scanner, the chromogen and the counterstain: calibrate on your own slides.
 DEFAULT_THRESHOLDS = (0.2, 0.2, 0.2)
-_DEFAULT_HOST_BAND = 512           # band rows of a host region when band_rows is not given
 
 _NAMED = {
     # Ruifrok & Johnston 2001, table of the H DAB vectors; the residual is the cross product
@@ -147,25 +147,6 @@ def _image_kind(img, what: str) -> Tuple[str, int, int, int]:
     return kind, B, H, W
 
 
-def _u8_batch(t: torch.Tensor, B: int, H: int, W: int, what: str) -> Tuple[torch.Tensor, int, int]:
-    """(tensor, row pitch, sample stride) in bytes of a uint8 [B, H, W, 3] GPU batch; a view whose pixels are not
-    contiguous within a row is copied."""
-    t = t if _u8_pixels_contiguous(t) else t.contiguous()
-    pitch = t.stride(1) if H > 1 else 3 * W
-    img = t.stride(0) if B > 1 else pitch * H
-    if pitch < 3 * W or img < pitch * H:
-        raise ValueError(f"{what}: uint8 image rows or samples overlap")
-    return t, pitch, img
-
-
-def _need_gpu(what: str, *tensors) -> torch.device:
-    if not all(t.is_cuda for t in tensors):
-        raise RuntimeError(f"stain2stain_amd: {what} needs GPU tensors (there is no CPU path)")
-    if any(t.device != tensors[0].device for t in tensors):
-        raise RuntimeError("stain2stain_amd: pred and target are on different devices")
-    return tensors[0].device
-
-
 def _chunks(cell_h: int, cell_w: int) -> int:
     n = ops._L().s2s_stain_quant_chunks(cell_h, cell_w)
     _native.check(n if n < 0 else 0, "stain_quant_chunks")
@@ -214,9 +195,9 @@ def _launch_batch(a: torch.Tensor, b: Optional[torch.Tensor], kind: str, B: int,
         rc = L.s2s_stain_quant_f32(a.data_ptr(), b.data_ptr() if paired else 0, int(paired), B, H, W, table, unmix,
                                    white, black, stain, part.data_ptr(), ops._stream())
     else:
-        a, pa, ia = _u8_batch(a, B, H, W, what)
+        a, pa, ia = batch_layout(a, what, copy=True)
         if paired:
-            b, pb, ib = _u8_batch(b, B, H, W, what)
+            b, pb, ib = batch_layout(b, what, copy=True)
         rc = L.s2s_stain_quant_u8(a.data_ptr(), pa, ia, b.data_ptr() if paired else 0, pb if paired else 0,
                                   ib if paired else 0, int(paired), B, 0, H, H, W, H, W, 0, -(-H // CHUNK_ROWS), table,
                                   unmix, white, black, stain, part.data_ptr(), ops._stream())
@@ -238,7 +219,7 @@ def stain_quantify(img: torch.Tensor, *, stains="hdab", thresholds: Sequence[flo
     kind, B, H, W = _image_kind(img, "stain_quantify")
     table, unmix = _kernel_args(stains, thresholds)
     white, black = _check_thresholds(white, black)
-    _need_gpu("stain_quantify", img)
+    gpu_device("stain_quantify", img, host_ok=False)
     with torch.no_grad():
         counts, sums, out = _launch_batch(img, None, kind, B, H, W, table, unmix, white, black, 0, "stain_quantify")
     return _single_dict(counts, sums, out, (B,))
@@ -256,7 +237,7 @@ def stain_agreement(pred: torch.Tensor, target: torch.Tensor, *, stain: int = 1,
     stain = _stain_index(stain)
     table, unmix = _kernel_args(stains, thresholds)
     white, black = _check_thresholds(white, black)
-    _need_gpu("stain_agreement", pred, target)
+    gpu_device("stain_agreement", pred, target, host_ok=False)
     with torch.no_grad():
         _, _, out = _launch_batch(pred, target, kind, B, H, W, table, unmix, white, black, stain, "stain_agreement")
     return _pair_dict(out, (B,))
@@ -266,13 +247,13 @@ def stain_separate(img: torch.Tensor, *, stains="hdab") -> torch.Tensor:
     """The stain concentrations of every pixel as fp32 ``[B, 3, H, W]``; input as ``stain_quantify``."""
     kind, B, H, W = _image_kind(img, "stain_separate")
     table, unmix = _kernel_args(stains, DEFAULT_THRESHOLDS)
-    dev = _need_gpu("stain_separate", img)
+    dev = gpu_device("stain_separate", img, host_ok=False)
     with torch.no_grad():
         out = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
         if kind == "f32":
             a, pitch, stride = img.detach().contiguous(), W, 3 * H * W
         else:
-            a, pitch, stride = _u8_batch(img, B, H, W, "stain_separate")
+            a, pitch, stride = batch_layout(img, "stain_separate", copy=True)
         rc = ops._L().s2s_stain_separate(a.data_ptr(), int(kind == "f32"), pitch, stride, B, H, W, table, unmix,
                                          out.data_ptr(), ops._stream())
         _native.check(rc, "stain_separate")
@@ -314,18 +295,6 @@ def plan_stain_bands(H: int, cell: int, band_rows: Optional[int] = None) -> List
     return bands
 
 
-def _check_region(img, what: str) -> Tuple[int, int]:
-    if not isinstance(img, torch.Tensor):
-        raise TypeError(f"{what}: the region must be a torch.Tensor, got {type(img).__name__}")
-    if img.dtype != torch.uint8:
-        raise ValueError(f"{what}: the region must be uint8, got {img.dtype}")
-    if img.dim() != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
-        raise ValueError(f"{what}: the region must be a non-empty [H, W, 3] RGB image, got {list(img.shape)}")
-    if not _u8_pixels_contiguous(img):
-        raise ValueError(f"{what}: pixels within a row must be contiguous")
-    return int(img.shape[0]), int(img.shape[1])
-
-
 def _check_cell(cell) -> int:
     cell = operator.index(cell)
     if cell < 1:
@@ -339,24 +308,21 @@ def _reduce_region(images, H: int, W: int, cell_h: int, cell_w: int, band_rows, 
     paired = len(images) == 2
     any_host = not all(t.is_cuda for t in images)
     if band_rows is None and any_host:
-        band_rows = _DEFAULT_HOST_BAND
+        band_rows = DEFAULT_HOST_BAND
     bands = plan_stain_bands(H, cell_h, band_rows)
-    gpu = [t.device for t in images if t.is_cuda]
-    if len(gpu) == 2 and gpu[0] != gpu[1]:
-        raise RuntimeError("stain2stain_amd: pred and target are on different devices")
-    dev = gpu[0] if gpu else torch.device("cuda", torch.cuda.current_device())
+    dev = gpu_device(what, *images)
     Gy, Gx = -(-H // cell_h), -(-W // cell_w)
     nchunk = _chunks(cell_h, cell_w)
     K = 5 if paired else 7
     buf_rows = max(r1 - r0 for _, _, r0, r1 in bands)
     with torch.no_grad():
-        src = [_BandSource(t, buf_rows, dev) for t in images]
+        src = [BandSource(t, buf_rows, dev) for t in images]
         part = _partials(dev, Gy * Gx, nchunk, K)
         L = ops._L()
         for g0, ng, r0, r1 in bands:
             views = [s.rows(r0, r1) for s in src]
-            pa, pitch_a = ops._u8_rows(views[0])
-            pb, pitch_b = ops._u8_rows(views[1]) if paired else (0, 0)
+            pa, pitch_a = gpu_rows(views[0])
+            pb, pitch_b = gpu_rows(views[1]) if paired else (0, 0)
             for gs in range(g0, g0 + ng, 65535):       # (grid.y)
                 n = min(65535, g0 + ng - gs)
                 rc = L.s2s_stain_quant_u8(pa, pitch_a, pitch_a * (r1 - r0), pb, pitch_b, pitch_b * (r1 - r0),
@@ -365,7 +331,7 @@ def _reduce_region(images, H: int, W: int, cell_h: int, cell_w: int, band_rows, 
                 _native.check(rc, what)
         res = _finalize(part, Gy * Gx, nchunk, paired, dev)
     stats_of.last_stats = {"bands": len(bands), "band_rows": buf_rows,
-                           "band_bytes": sum(0 if s.on_gpu else s.band.numel() for s in src)}
+                           "band_bytes": sum(s.band_bytes for s in src)}
     return res, (Gy, Gx)
 
 
@@ -382,7 +348,7 @@ def region_stain_map(region_u8: torch.Tensor, *, cell: int = 256, band_rows: Opt
     index depends on the region alone: the result is bit-equal for every ``band_rows`` and for host and GPU input.
     ``region_stain_map.last_stats``: bands, band_rows, band_bytes of the last call.  Other arguments as
     ``stain_quantify``."""
-    H, W = _check_region(region_u8, "region_stain_map")
+    H, W, _ = check_region(region_u8, "region_stain_map")
     cell, stain = _check_cell(cell), _stain_index(stain)
     table, unmix = _kernel_args(stains, thresholds)
     white, black = _check_thresholds(white, black)
@@ -403,8 +369,8 @@ def region_stain_agreement(pred_u8: torch.Tensor, target_u8: torch.Tensor, *, ce
     fp32 device scalars, or ``[Gy, Gx]`` grids per ``cell`` x ``cell`` cell when ``cell`` is given.  Banding and its
     bit equality as ``region_stain_map``."""
     _check_pair(pred_u8, target_u8, "region_stain_agreement")
-    H, W = _check_region(pred_u8, "region_stain_agreement")
-    _check_region(target_u8, "region_stain_agreement")
+    H, W, _ = check_region(pred_u8, "region_stain_agreement")
+    check_region(target_u8, "region_stain_agreement")
     stain = _stain_index(stain)
     ch, cw = (H, W) if cell is None else (min(_check_cell(cell), H), min(_check_cell(cell), W))
     table, unmix = _kernel_args(stains, thresholds)

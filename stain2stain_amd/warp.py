@@ -35,14 +35,13 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import _native, ops
+from ._regionio import DEFAULT_HOST_BAND, BandSink, BandSource, batch_layout, check_region, gpu_device
 from .registration import region_shift_field
-from .image_metrics import _u8_pixels_contiguous
 
 SUB = 16                     # displacement units per pixel
 MAX_SHIFT = 1024             # WP_MAX_SHIFT of csrc/warp.hip
 MAX_CELLS = 65536            # nodes of a field: the cleaning kernel is one workgroup
 MAX_CELL = 1 << 14           # span^2 times an int32 node stays inside int64
-_DEFAULT_HOST_BAND = 512     # output rows per band of a host region
 
 _CLEAN_KEYS = ("min_score", "min_margin", "max_dev")
 _WARP_KEYS = ("fill", "band_rows")
@@ -60,14 +59,6 @@ def _check_fill(fill, what: str) -> int:
     if not 0 <= fill <= 255:
         raise ValueError(f"{what}: fill must lie in 0..255, got {fill}")
     return fill
-
-
-def _gpu_device(t: torch.Tensor, what: str) -> torch.device:
-    if t.is_cuda:
-        return t.device
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"stain2stain_amd: {what} needs a GPU (there is no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 # ---- cleaning ----------------------------------------------------------------------------------------------------------
@@ -141,52 +132,6 @@ def clean_shift_field(field_or_shift, *, reliable: Optional[torch.Tensor] = None
 
 
 # ---- the warp ----------------------------------------------------------------------------------------------------------
-class _Bands:
-    """Rows [r0, r1) of a host uint8 region as a GPU view, through one pinned staging buffer and one band buffer (in the
-    manner of ``image_metrics._BandSource``, for images and masks alike)."""
-
-    def __init__(self, img: torch.Tensor, rows: int, device):
-        shape = (rows,) + tuple(img.shape[1:])
-        self.img = img
-        self.stage = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
-        self.band = torch.empty(shape, dtype=torch.uint8, device=device)
-        self.ready = None                                      # the GPU's last read of the staging buffer
-
-    def rows(self, r0: int, r1: int) -> torch.Tensor:
-        if self.ready is not None:
-            self.ready.synchronize()                           # the previous upload has left the staging buffer
-        n = r1 - r0
-        self.stage[:n].copy_(self.img[r0:r1])
-        self.band[:n].copy_(self.stage[:n], non_blocking=True)
-        self.ready = torch.cuda.Event()
-        self.ready.record()
-        return self.band[:n]
-
-
-def _check_warp_region(t, what: str):
-    """(H, W, C) of a uint8 [H, W, 3] image or [H, W] mask whose pixels are contiguous within a row."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{what}: the region must be a torch.Tensor, got {type(t).__name__}")
-    if t.dtype != torch.uint8:
-        raise ValueError(f"{what}: the region must be uint8, got {t.dtype}")
-    if t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] != 3) or min(t.shape) < 1:
-        raise ValueError(f"{what}: the region must be a non-empty [H, W, 3] image or [H, W] mask, got {list(t.shape)}")
-    H, W = int(t.shape[0]), int(t.shape[1])
-    if t.dim() == 3:
-        if not _u8_pixels_contiguous(t):
-            raise ValueError(f"{what}: pixels within a row must be contiguous")
-    elif W > 1 and t.stride(1) != 1:
-        raise ValueError(f"{what}: pixels within a row must be contiguous")
-    return H, W, 3 if t.dim() == 3 else 1
-
-
-def _pitch(t: torch.Tensor, W: int, C: int, what: str) -> int:
-    pitch = t.stride(0) if t.shape[0] > 1 else W * C
-    if pitch < W * C:
-        raise ValueError(f"{what}: the rows of the region overlap")
-    return pitch
-
-
 def _check_field(field, H: int, W: int, cell: int, what: str):
     if not isinstance(field, torch.Tensor):
         raise TypeError(f"{what}: field must be a torch.Tensor, got {type(field).__name__}")
@@ -214,10 +159,10 @@ def warp_region(region_u8: torch.Tensor, field: torch.Tensor, cell: int, *, max_
     input's device.  ``field``: int32 ``[H // cell, W // cell, 2]`` in 1/16 pixel on the device, any values: the kernel
     clamps the displacement to ``max_shift`` pixels.  A GPU region is warped in one launch (``band_rows`` rows per launch
     when given).  A host region is streamed in bands of ``band_rows`` output rows (``None``: 512) with a halo of
-    ``max_shift + 1`` rows through pinned staging, which waits for the previous upload and for each band to land.  The
+    ``max_shift + 1`` rows through pinned staging in both directions, a band's download overlapping the next band's upload.  The
     bytes do not depend on ``band_rows`` or on where the region lives."""
     what = "warp_region"
-    H, W, C = _check_warp_region(region_u8, what)
+    H, W, C = check_region(region_u8, what, mask_ok=True)
     cell = operator.index(cell)
     max_shift, fill = _check_max_shift(max_shift, what), _check_fill(fill, what)
     if band_rows is not None:
@@ -225,11 +170,11 @@ def warp_region(region_u8: torch.Tensor, field: torch.Tensor, cell: int, *, max_
         if band_rows < 1:
             raise ValueError(f"{what}: band_rows must be positive, got {band_rows}")
     Gy, Gx = _check_field(field, H, W, cell, what)
-    dev = _gpu_device(region_u8, what)
+    dev = gpu_device(what, region_u8)
     if field.device != dev:
         raise ValueError(f"{what}: field must be on the region's device")
     on_gpu = region_u8.is_cuda
-    step = min(band_rows or (H if on_gpu else _DEFAULT_HOST_BAND), H)
+    step = min(band_rows or (H if on_gpu else DEFAULT_HOST_BAND), H)
     halo = max_shift + 1
     L = ops._L()
     rowb = W * C
@@ -238,17 +183,15 @@ def warp_region(region_u8: torch.Tensor, field: torch.Tensor, cell: int, *, max_
         fp = field.data_ptr()
         if on_gpu:
             out = torch.empty(tuple(region_u8.shape), dtype=torch.uint8, device=dev)
-            pitch = _pitch(region_u8, W, C, what)
+            pitch = batch_layout(region_u8[None], what, "the region")[1]
             for r0 in range(0, H, step):
                 n = min(step, H - r0)
                 rc = L.s2s_warp_region_u8(region_u8.data_ptr(), pitch, 0, H, fp, Gy, Gx, cell, max_shift, H, W, C, fill,
                                           r0, n, out.data_ptr() + r0 * rowb, rowb, ops._stream())
                 _native.check(rc, what)
             return out
-        src = _Bands(region_u8, min(step + 2 * halo, H), dev)
+        src, sink = BandSource(region_u8, min(step + 2 * halo, H), dev), BandSink(region_u8.shape, step)
         band = torch.empty((step,) + tuple(region_u8.shape[1:]), dtype=torch.uint8, device=dev)
-        stage = torch.empty((step,) + tuple(region_u8.shape[1:]), dtype=torch.uint8, pin_memory=True)
-        out = torch.empty(tuple(region_u8.shape), dtype=torch.uint8)
         for r0 in range(0, H, step):
             n = min(step, H - r0)
             s0, s1 = max(0, r0 - halo), min(H, r0 + n + halo)
@@ -256,10 +199,8 @@ def warp_region(region_u8: torch.Tensor, field: torch.Tensor, cell: int, *, max_
             rc = L.s2s_warp_region_u8(rows.data_ptr(), rowb, s0, s1 - s0, fp, Gy, Gx, cell, max_shift, H, W, C, fill,
                                       r0, n, band.data_ptr(), rowb, ops._stream())
             _native.check(rc, what)
-            stage[:n].copy_(band[:n], non_blocking=True)
-            torch.cuda.current_stream().synchronize()          # the band has landed in the staging buffer
-            out[r0:r0 + n].copy_(stage[:n])
-    return out
+            sink.put(band, r0, r0 + n)
+        return sink.close()[0]
 
 
 def register_region(src_region_u8: torch.Tensor, tgt_region_u8: torch.Tensor, cell: int = 256, *,
@@ -280,11 +221,11 @@ def register_region(src_region_u8: torch.Tensor, tgt_region_u8: torch.Tensor, ce
     warp_kw = {k: kwargs.pop(k) for k in _WARP_KEYS if k in kwargs}
     mask_fill = _check_fill(kwargs.pop("mask_fill", 0), what)
     masks = list(masks)
-    H, W, C = _check_warp_region(tgt_region_u8, what)
+    H, W, C = check_region(tgt_region_u8, what, mask_ok=True)
     if C != 3:
         raise ValueError(f"{what}: the regions must be [H, W, 3] RGB images, got {list(tgt_region_u8.shape)}")
     for m in masks:
-        if _check_warp_region(m, what) != (H, W, 1):
+        if check_region(m, what, mask_ok=True) != (H, W, 1):
             raise ValueError(f"{what}: a mask must be uint8 [{H}, {W}], got {list(m.shape)}")
     measured = region_shift_field(src_region_u8, tgt_region_u8, cell, **kwargs)
     cleaned = clean_shift_field(measured, max_shift=max_shift, **clean_kw)

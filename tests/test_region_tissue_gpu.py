@@ -125,11 +125,11 @@ def test_count_outside_the_band_is_flagged():
 
 # ---- every tile kept: the call without the keywords, bit for bit -----------------------------------------------------
 @pytest.mark.parametrize("H,W,T,overlap,batch", [(150, 130, 32, 8, 4), (37, 45, 64, 16, 3)])
-@pytest.mark.parametrize("cm", [0, 2])
-def test_all_kept_equals_the_plain_call(H, W, T, overlap, batch, cm):
+@pytest.mark.parametrize("cm,on_gpu", [(0, True), (2, True), (2, False)], ids=["0", "2", "2-host"])
+def test_all_kept_equals_the_plain_call(H, W, T, overlap, batch, cm, on_gpu):
     from stain2stain_amd import translate_region
     from stain2stain_amd.region import plan_tiles
-    img = _img(H, W, 3).to(DEV)
+    img = _img(H, W, 3).to(DEV) if on_gpu else _img(H, W, 3)      # a host image: both staging directions
     kw = dict(tile=T, overlap=overlap, batch=batch, return_float=True)
     s0 = _Pointwise(cm)
     plain = translate_region(img, s0, **kw)
