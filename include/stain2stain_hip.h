@@ -765,6 +765,32 @@ int s2s_warp_region_u8(const void* src, long src_pitch, int src_row0, int src_ro
                        int cell, int max_shift, int H, int W, int C, int fill, int row0, int rows, void* out,
                        long out_pitch, void* stream);
 
+/* ---- rigid region pre-alignment: overview maps and the rigid warp (rigid.hip) -----
+ * s2s_structure_overview_u8: img = rows of a uint8 [H][W][3] region, any pitch >= 3 W and any base alignment; q_table and
+ *   w HOST, as s2s_structure_map_u8 takes them; f the structure byte of that entry point; ds a power of two in 1 .. 64;
+ *   out uint8 [H / ds][W / ds], contiguous = (sum of the ds x ds block of f + ds^2 / 2) / ds^2 over whole blocks (the sum
+ *   is at most 64^2 255 < 2^32).  For ds in {1, 2, 4} this is s2s_structure_map_u8 bit for bit.  Shape status for another
+ *   ds, H or W below ds or above 2^30, a pitch below a row, or a table and weights that could overflow int32.  One launch.
+ * s2s_rigid_warp_u8: a transform is long [6] = (c, s, ty, tx, Cy, Cx): cosine and sine in Q24, the translation in 1/16
+ *   pixel, the doubled centre (the centre of an H-row region is Cy = H - 1).  The kernel clamps c, s to +-2^24, ty, tx to
+ *   +-2^36 and Cy, Cx to +-2^24.  For output pixel (y, x) with the displacement (dy, dx) in 1/16 pixel -- 0 when field is
+ *   null, else the dense displacement of s2s_warp_region_u8, its +-16 max_shift clamp included -- in 64 bits:
+ *     Uy = 32 y + 2 dy - 16 Cy, Ux = 32 x + 2 dx - 16 Cx; Vy = c Uy - s Ux, Vx = s Uy + c Ux;
+ *     sy = ((Vy + Cy 2^28 + 2^24) >> 25) + ty (arithmetic shift), sx likewise with Cx and tx.
+ *   That is out[p] = T[C + R (p + d - C) + t] with R = [[cos, -sin], [sin, cos]] acting on (y, x).  Sampling at (sy, sx)
+ *   is that of s2s_warp_region_u8: nearest = 0 bilinear in 1/16 pixel with fill for a tap outside, nearest = 1 the tap at
+ *   ((sy + 8) >> 4, (sx + 8) >> 4); either for C = 3 and for C = 1.  transform DEVICE long [A][6], any values: result a is
+ *   written at out + a out_img.  src = rows [src_row0, src_row0 + src_rows) of the region; out = rows [row0, row0 + rows)
+ *   of each result; a tap on a row that is not present takes the fill, so the caller provides the rows a band reads; no
+ *   read leaves the rows present whatever the transform and the field hold.  Shape status for H or W outside 1 .. 2^20,
+ *   A outside 1 .. 65535, a bad C, nearest, fill or band, a pitch smaller than a row, out_img < out_pitch rows for A > 1,
+ *   and with a field the grid conditions of s2s_warp_region_u8.  One launch; the result does not depend on the banding. */
+int s2s_structure_overview_u8(const void* img, long pitch, int H, int W, const int* q_table, const int* w, int ds,
+                              void* out, void* stream);
+int s2s_rigid_warp_u8(const void* src, long src_pitch, int src_row0, int src_rows, const long* transform, int A,
+                      const int* field, int Gy, int Gx, int cell, int max_shift, int H, int W, int C, int nearest,
+                      int fill, int row0, int rows, void* out, long out_pitch, long out_img, void* stream);
+
 /* ---- tile quality control: focus, ink and dark-artefact counts (qc.hip) -----------
  * Integer throughout.  mx / mn = max / min(R, G, B); tissue = mn < white and mx >= black; Y = (77 R + 150 G + 29 B + 128)
  * >> 8; L(y, x) = Y(y-1, x) + Y(y+1, x) + Y(y, x-1) + Y(y, x+1) - 4 Y(y, x); a focus pixel is a tissue pixel with

@@ -32,6 +32,8 @@ from .augment import (PairedAugmenter, paired_augment, sample_d4_params, sample_
 from .registration import (overlap_boxes, region_shift_field, register_pairs, registered_quality,
                            sample_crop_params_within, shift_tiles, structure_map, structure_weights)
 from .warp import clean_shift_field, register_region, warp_region
+from .rigid import (align_regions, register_rigid, rigid_transform, rigid_warp, rotation_table,
+                    structure_overview)
 from .qc import qc_keep, region_qc, region_qc_map, tile_qc, window_sums
 from .morphology import distance_transform, fill_holes, mask_boundary, mask_boundary_agreement, mask_morphology
 from .object_features import (object_feature_summary, object_features, region_stain_object_features,
@@ -53,6 +55,7 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "PairedAugmenter", "structure_weights", "structure_map", "register_pairs", "shift_tiles", "overlap_boxes",
            "sample_crop_params_within", "registered_quality", "region_shift_field",
            "clean_shift_field", "warp_region", "register_region",
+           "structure_overview", "rigid_warp", "register_rigid", "align_regions", "rotation_table", "rigid_transform",
            "tile_qc", "region_qc", "region_qc_map", "qc_keep", "window_sums",
            "distance_transform", "mask_morphology", "fill_holes", "mask_boundary", "mask_boundary_agreement",
            "object_features", "stain_object_features", "region_stain_object_features", "object_feature_summary",
