@@ -263,8 +263,9 @@ __global__ __launch_bounds__(256) void pack_conv3x3_batched_kernel(const PackDes
   const int nci = (Cin + 31) / 32;
   const int t = blockIdx.x - (int)d.start;
   const int co0 = (t / nci) * 32, ci0 = (t % nci) * 32;
-  // rows of 288 contiguous floats (32 ci x 9 taps): 16-byte loads when the tile is whole and the row base aligned
-  const bool whole = co0 + 32 <= Cout && ci0 + 32 <= Cin && ((Cin * 9) % 4) == 0;
+  // rows of 288 contiguous floats (32 ci x 9 taps): 16-byte loads when the tile is whole and every row base aligned
+  // (a multiple of 4 floats from a 16-byte aligned `w`; a `w` that is a view into a larger buffer need not be)
+  const bool whole = co0 + 32 <= Cout && ci0 + 32 <= Cin && ((Cin * 9) % 4) == 0 && (d.w & 15) == 0;
   if (whole) {
     for (int idx = threadIdx.x; idx < 32 * 72; idx += 256) {
       const int co = idx / 72, j4 = idx - co * 72;
