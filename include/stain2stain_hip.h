@@ -819,6 +819,52 @@ int s2s_qc_windows_u8(const void* img, long pitch, long img_stride, int B, int b
 int s2s_qc_finalize(const long* slab, long owners, int nchunk, int accumulate, const int* origins, int n, int H, int W,
                     int win_h, int win_w, long* counts, double* derived, void* stream);
 
+/* ---- result rendering: overlays, heat maps, comparisons, thumbnails (render.hip) ---
+ * Integer throughout.  mix(b, c, a) = (b (256 - a) + c a + 128) >> 8 per channel, a in 0 .. 256: a = 0 returns b and
+ * a = 256 returns c exactly.  A region is a base pointer, a row pitch in bytes (any pitch >= a row, any base alignment),
+ * H and W, both in 1 .. 2^30.  A launch writes rows [row0, row0 + rows); base, a, b and out point at row row0.  An input
+ * that is read at neighbouring rows is present at rows [src_row0, src_row0 + src_rows) and points at row src_row0.
+ * Everything is computed from global coordinates, so the bytes do not depend on the banding.  A null pointer returns the
+ * null status and every shape, range or pitch violation the shape status, before any HIP call.  out may be base itself
+ * (same pointer and pitch): an output pixel reads only its own base pixel.  One launch each.
+ * s2s_render_classes_u8 / s2s_render_labels_u8: base uint8 [H][W][3]; a uint8 class mask [H][W] or an int label image
+ *   [H][W] (pitch in bytes, a multiple of 4; the pointer dword-aligned, else the alignment status); palette DEVICE uint8
+ *   [256][3]; fill_alpha DEVICE int [256], entries in 0 .. 256 (the kernel clamps them); edge radius r in 0 .. 4;
+ *   edge_alpha in 0 .. 256; edge_rgb = -1 (the edge takes the palette colour) or 0xRRGGBB.  Per pixel p: id(p) = the mask
+ *   byte, or max(L, 0); k(p) = the mask byte, or 0 for L <= 0 and ((L - 1) mod 255) + 1 otherwise.  p is an edge pixel iff
+ *   r >= 1, id(p) != 0 and some offset with 1 <= |dy| + |dx| <= r leads to a pixel q outside [0, H) x [0, W) of the whole
+ *   region or with id(q) != id(p): identities are compared, not colours; with r = 1 on a binary mask this is the rule of
+ *   s2s_mask_boundary.  out = mix(base, edge colour, edge_alpha) on edge pixels, mix(base, palette[k], fill_alpha[k])
+ *   otherwise.  Shape status unless the mask rows present cover [max(0, row0 - r), min(H, row0 + rows + r)); the kernel
+ *   tests every neighbour against the region, so no mask content moves a read.
+ * s2s_render_heat_u8: Q DEVICE int [Gy][Gx], one node per cell x cell cell, Gy in {H / cell, ceil(H / cell)} and >= 1, Gx
+ *   alike, Gy Gx <= 65536, cell in 1 .. 2^14; lut DEVICE uint8 [256][3]; alpha and min_index in 0 .. 256; smooth 0 or 1.
+ *   smooth = 0: g = min(p / cell, G - 1) per axis, d = Q[gy][gx].  smooth = 1: the dense interpolation of
+ *   s2s_warp_region_u8 with D = Q (nodes at the cell centres, doubled coordinates, span = 2 cell, the nearest node outside
+ *   the centres), d = floor((num + span^2 / 2) / span^2), without the max_shift clamp.  d is clamped to 0 .. 65280 =
+ *   255 * 256 by the kernel, whatever Q holds (num < 2^46 for nodes in range, below 2^62 for any int).  idx = (d + 128)
+ *   >> 8; out = mix(base, lut[idx], alpha) where idx >= min_index, base otherwise.
+ * s2s_render_compare_u8: a, b uint8 [H][W][3].  mode 0: a where (y / cell + x / cell) is even, b otherwise; mode 1:
+ *   mix(a, b, alpha); mode 2: min(255, |a - b| gain).  cell in 1 .. 2^30, alpha in 0 .. 256, gain in 1 .. 255, each
+ *   checked whatever the mode.
+ * s2s_box_down_u8: src = rows [src_row0, src_row0 + src_rows) of a uint8 [H][W][C] region, C = 3 or 1; f in 1 .. 256; out
+ *   = rows [row0, row0 + rows) of the uint8 [ceil(H / f)][ceil(W / f)][C] result.  An output pixel covers the n pixels of
+ *   its f x f block that lie inside the region.  C = 3: floor((2 sum + n) / (2 n)) (sum <= 255 * 65536); C = 1: the
+ *   maximum.  Shape status unless the source rows present cover [row0 f, min(H, (row0 + rows) f)).  f = 1 is a copy. */
+int s2s_render_classes_u8(const void* base, long base_pitch, const void* mask, long mask_pitch, int mask_row0,
+                          int mask_rows, const void* palette, const int* fill_alpha, int r, int edge_alpha, int edge_rgb,
+                          int H, int W, int row0, int rows, void* out, long out_pitch, void* stream);
+int s2s_render_labels_u8(const void* base, long base_pitch, const int* labels, long labels_pitch, int labels_row0,
+                         int labels_rows, const void* palette, const int* fill_alpha, int r, int edge_alpha, int edge_rgb,
+                         int H, int W, int row0, int rows, void* out, long out_pitch, void* stream);
+int s2s_render_heat_u8(const void* base, long base_pitch, const int* Q, int Gy, int Gx, int cell, const void* lut,
+                       int alpha, int min_index, int smooth, int H, int W, int row0, int rows, void* out, long out_pitch,
+                       void* stream);
+int s2s_render_compare_u8(const void* a, long a_pitch, const void* b, long b_pitch, int mode, int cell, int alpha, int gain,
+                          int H, int W, int row0, int rows, void* out, long out_pitch, void* stream);
+int s2s_box_down_u8(const void* src, long src_pitch, int src_row0, int src_rows, int H, int W, int C, int f, int row0,
+                    int rows, void* out, long out_pitch, void* stream);
+
 /* ---- loss variants and class conditioning (loss_variants.hip) -- SURVEY section 8 row f4 -----------------
  * ROI-weighted MSE (conditional_flow_matching_masked.py:76-90): w = 1 + roi_lambda * mask,
  *   out[0] = sum(w (v-u)^2) / (sum(w) + 1e-8), w broadcast over C.  v, u: float[B][C][HW]; mask: float[B][HW];

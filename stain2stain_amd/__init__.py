@@ -39,6 +39,8 @@ from .morphology import distance_transform, fill_holes, mask_boundary, mask_boun
 from .object_features import (object_feature_summary, object_features, region_stain_object_features,
                               stain_object_features)
 from .split import label_agreement, split_objects, stain_object_split
+from .render import (colormap, compare_regions, compose_panels, default_palette, downsample_region, render_classes,
+                     render_heat, render_region)
 
 __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeEmbedding", "FlowUNet",
            "ConditionalFlowMatcher", "ConditionalFlowMatchingModule", "MultiTaskFlowMatchingModule", "euler_generate", "dopri5_generate", "euler_integrate", "dopri5_integrate", "SolverConfig", "GraphedVelocity",
@@ -59,4 +61,6 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "tile_qc", "region_qc", "region_qc_map", "qc_keep", "window_sums",
            "distance_transform", "mask_morphology", "fill_holes", "mask_boundary", "mask_boundary_agreement",
            "object_features", "stain_object_features", "region_stain_object_features", "object_feature_summary",
-           "split_objects", "stain_object_split", "label_agreement"]
+           "split_objects", "stain_object_split", "label_agreement",
+           "render_classes", "render_heat", "compare_regions", "downsample_region", "render_region", "compose_panels",
+           "default_palette", "colormap"]
