@@ -541,6 +541,53 @@ int s2s_stain_conc_hist_u8(const void* img, long pitch, long img_stride, int B, 
 int s2s_stain_normalize_u8(const void* img, long pitch, long img_stride, int B, int H, int W, const float* od_table,
                            const float* coef, void* out, long out_pitch, long out_img, int out_f32, void* stream);
 
+/* ---- stain threshold calibration: per-owner histograms, Otsu / triangle (stain_calibrate.hip) ---
+ * Images, od_table, unmix (the first nine floats are read), white and black as in stain quantification; c_k and the
+ * tissue rule are the same.  bin(c) = clamp(ceil(c * 1024) - 1, 0, 4095), every operation in fp32, clamped as a float:
+ * bin(c) >= j <=> c > j / 1024 for j in 1..4095.  An owner is one sample (pool == 0: B owners) or the whole batch
+ * (pool != 0: one owner) and holds at most 2^40 pixels (H W, or B H W pooled); B <= 65535.
+ * s2s_stain_hist_u8 / _f32: hist long [owners][3][4096]: hist[o][k][b] += the tissue pixels of owner o with
+ *   bin(c_k) = b, for the stains k of stain_mask (bits 0..2, not empty; the other rows are not touched by the counting);
+ *   tissue long [owners] += the tissue pixels.  Both are ADDED to with 64-bit integer atomics (bit-reproducible; bands
+ *   and repeated calls add up); reset != 0 zeroes all of hist and tissue first, in a launch of its own on the same
+ *   stream.  The uint8 buffers hold image rows [band_top, band_top + band_h) of B images (pitch, img_stride in bytes, any
+ *   alignment); float input is [B][3][H][W] in the network's range through the save conversion.
+ * s2s_stain_pair_hist_u8 / _f32: for stain `stain` of a prediction a and a target b, hist long [owners][4][4096]:
+ *   [0] a's tissue by bin_a, [1] b's tissue by bin_b, [2] tissue in both by min(bin_a, bin_b), [3] tissue in both with
+ *   bin_b >= jt by bin_a (jt in 1..4095; jt == 0: row 3 is not counted); tissue long [owners][2] (a, b).
+ *   A launch whose workgroups would count 2^32 pixels or more each is refused (a uint32 bin in LDS could wrap).
+ * s2s_stain_thresholds: hist long [rows][4096] -> positive long [rows][4096], positive[j] = sum over b >= j of hist[b];
+ *   bins / valid int [rows][2 + nquant], thr double [rows][2 + nquant] = bins / 1024: column 0 Otsu (S1[j] = sum over
+ *   b >= j of b hist[b], N = positive[0], S = S1[0]; sigma(j) = a a / (double(P) double(N - P)) with P = positive[j] and
+ *   a = double(N S1[j] - P S) formed exactly and rounded once, 0 when P is 0 or N; the smallest j >= 1 of maximal sigma;
+ *   valid 0 and bin 0 when every sigma is 0), column 1 the triangle rule on the histogram summed in groups of `coarse`
+ *   (a power of two in 1..4096) bins: p the smallest index of the maximal group g, e the largest non-empty index,
+ *   T(i) = g[p] (e - p) + (g[e] - g[p]) (i - p) - g[i] (e - p) for p < i < e, bin = coarse * (the smallest i of maximal
+ *   T); valid 0 and bin 0 when e <= p + 1), columns 2.. the quantiles (a HOST array of nquant <= 8 doubles in [0, 1]):
+ *   the smallest j >= 1 with positive[j] <= floor(q double(N)); 4095 and valid 0 when there is none or N = 0.
+ * s2s_stain_pair_thresholds: hist long [owners][4][4096] -> counts long [owners][4][4096] = the suffix sums positive_a,
+ *   positive_b, both_common, both_cond; dice double [owners][2][4096] = 2 both_common / (positive_a + positive_b) and
+ *   2 both_cond / (positive_a + positive_b[jt]), 1 where the denominator is 0 (the second row is 0 without jt); bins /
+ *   valid int [owners][2]: the smallest j >= 1 of minimal |positive_a[j] N_b - positive_b[jt] N_a| and the smallest
+ *   j >= 1 of maximal conditional Dice, both compared exactly in 128 bits; valid iff jt > 0 and both images have
+ *   tissue.  vals double [owners][8]: the two thresholds, Dice and the prediction's burden at the best-Dice bin, the
+ *   target's burden at jt, the prediction's burden, |burden difference| and Dice at the burden-matching bin. */
+int s2s_stain_hist_u8(const void* img, long pitch, long img_stride, int B, int band_top, int band_h, int H, int W,
+                      const float* od_table, const float* unmix, int white, int black, int stain_mask, int pool,
+                      int reset, long* hist, long* tissue, void* stream);
+int s2s_stain_hist_f32(const float* img, int B, int H, int W, const float* od_table, const float* unmix, int white,
+                       int black, int stain_mask, int pool, int reset, long* hist, long* tissue, void* stream);
+int s2s_stain_pair_hist_u8(const void* a, long pitch_a, long img_a, const void* b, long pitch_b, long img_b, int B,
+                           int band_top, int band_h, int H, int W, const float* od_table, const float* unmix, int white,
+                           int black, int stain, int jt, int pool, int reset, long* hist, long* tissue, void* stream);
+int s2s_stain_pair_hist_f32(const float* a, const float* b, int B, int H, int W, const float* od_table,
+                            const float* unmix, int white, int black, int stain, int jt, int pool, int reset, long* hist,
+                            long* tissue, void* stream);
+int s2s_stain_thresholds(const long* hist, long rows, int coarse, const double* quantiles, int nquant, long* positive,
+                         int* bins, int* valid, double* thr, void* stream);
+int s2s_stain_pair_thresholds(const long* hist, long owners, int jt, long* counts, double* dice, int* bins, int* valid,
+                              double* vals, void* stream);
+
 /* ---- stain object analysis: connected-component labelling (objects.hip) -----------
  * A sample is H x W <= 2^31 - 2 pixels and has an index space of its own: nothing joins two samples.  B <= 65535.
  * s2s_objects_words(B, H, W): the int32 words of scratch s2s_objects_label needs (parents, then chunk counts);

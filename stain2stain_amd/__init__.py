@@ -25,6 +25,9 @@ from .region import multitask_sampler, plan_region_batches, plan_tiles, tissue_c
 from .image_metrics import generation_quality, image_quality, plan_bands, region_quality
 from .stain_quant import (region_stain_agreement, region_stain_map, stain_agreement, stain_matrix, stain_quantify,
                           stain_separate)
+from .stain_calibrate import (calibrate_thresholds, match_thresholds, region_stain_histogram,
+                              region_stain_pair_histogram, stain_histogram, stain_pair_histogram, stain_thresholds,
+                              thresholds_tuple)
 from .stain_norm import REFERENCE_HE, StainFit, fit_stains, normalize_region, stain_normalize
 from .objects import label_components, region_stain_objects, stain_object_agreement, stain_objects
 from .augment import (PairedAugmenter, paired_augment, sample_d4_params, sample_stain_jitter, stain_augment,
@@ -63,4 +66,6 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "object_features", "stain_object_features", "region_stain_object_features", "object_feature_summary",
            "split_objects", "stain_object_split", "label_agreement",
            "render_classes", "render_heat", "compare_regions", "downsample_region", "render_region", "compose_panels",
-           "default_palette", "colormap"]
+           "default_palette", "colormap",
+           "stain_histogram", "region_stain_histogram", "stain_thresholds", "calibrate_thresholds", "thresholds_tuple",
+           "stain_pair_histogram", "region_stain_pair_histogram", "match_thresholds"]
