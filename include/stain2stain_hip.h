@@ -588,6 +588,73 @@ int s2s_stain_thresholds(const long* hist, long rows, int coarse, const double* 
 int s2s_stain_pair_thresholds(const long* hist, long owners, int jt, long* counts, double* dice, int* bins, int* valid,
                               double* vals, void* stream);
 
+/* ---- zonal stain quantification: burden and objects per class of a zone map (zonal.hip) ----------
+ * Images, od_table, unmix (twelve floats: m, then the three thresholds), white and black as in stain quantification; c_k,
+ * the tissue rule and "positive" (tissue and c_k > thr_k) are the same.  q_k = min((int)rintf(fmaxf(c_k, 0) * 1024),
+ * 4095) as in s2s_objfeat_intensity_*, but summed over TISSUE pixels only.  zones: one byte per pixel, [B][.][.] with
+ * zone_pitch and zone_stride in bytes (any pitch >= W, any alignment); num_zones = Z in 1..256; a pixel whose byte is
+ * >= Z belongs to no zone.  An owner is one sample (pool == 0: B owners) or the whole batch (pool != 0: one owner) and
+ * holds at most 2^40 pixels; B <= 65535.  The grid is at most one resident round (2048 workgroups over all owners, 1792 paired); a
+ * launch whose workgroups would take 2^20 pixels or more each is refused with the shape status before any launch (a
+ * uint32 cell of the workgroup's LDS table holds at most pixels * 4095).
+ * s2s_zonal_u8 / _f32: table long [owners][Z][8] += pixels, tissue, positive_0, positive_1, positive_2, sum q_0, sum q_1,
+ *   sum q_2 of the owner's pixels of each zone; unzoned long [owners] += the pixels of no zone.  Both are ADDED to with
+ *   64-bit integer atomics (bit-reproducible; bands and repeated calls add up); reset != 0 zeroes table and unzoned
+ *   first, in a launch of its own on the same stream.  The uint8 image and zone buffers hold rows [band_top, band_top +
+ *   band_h) of B images of H x W pixels; float input is [B][3][H][W] in the network's range through the save conversion,
+ *   with the zones of all H rows.
+ * s2s_zonal_pair_u8 / _f32: for stain `stain` of a prediction a and a target b over one zone map, table long
+ *   [owners][Z][6] += pixels, tissue_a, tissue_b, positive in both, in a only, in b only.
+ * s2s_zonal_finalize: one thread per (owner, zone), fp64, no contraction, in this order.  paired == 0: out double
+ *   [owners][Z][8]: td = (double)max(tissue, 1);
+ *     0..2  burden_k = (double)positive_k / td
+ *     3..5  mean_conc_k = ((double)sum q_k / td) / 1024
+ *     6     tissue_frac = (double)tissue / (double)max(pixels, 1)
+ *     7     area_frac = (double)pixels / (double)max(N, 1), N = unzoned[owner] + the sum over the owner's zones of pixels
+ *   paired != 0 (unzoned may be null): out double [owners][Z][5]: na = both + a_only, nb = both + b_only;
+ *     0, 1  burden_pred = (double)na / (double)max(tissue_a, 1), burden_target = (double)nb / (double)max(tissue_b, 1)
+ *     2     burden_abs_err = fabs(burden_pred - burden_target)
+ *     3     dice = (double)(2 * both) / (double)(na + nb), 1 when na + nb == 0
+ *     4     iou = (double)both / (double)(both + a_only + b_only), 1 when that is 0
+ * s2s_zonal_object_overlap: labels int [B][H][W], dense, as s2s_objfeat_shape reads them (0 = background, objects
+ *   1..count, M = max_objects >= 1, labels above M not tabulated); H, W <= 32767; B M Z < 2^31, refused with the shape
+ *   status otherwise.  overlap int [B][M][Z] += the pixels of object m + 1 whose zone byte is z < Z; area int [B][M] +=
+ *   all pixels of object m + 1; count int [B] = max(count, the largest label).  The CALLER ZEROES all three.  One launch.
+ * s2s_zonal_object_assign: one wave per row (b, m).  The zone of an object is the z of largest overlap, ties to the
+ *   smaller z: zone int [B][M] = it, zone_pixels long [B][M] = that overlap; -1 and 0 when every overlap is 0 and in rows
+ *   at or beyond min(count, M).  objects long [B][Z] += 1 and object_pixels long [B][Z] += area at the object's zone (the
+ *   caller zeroes both).
+ * s2s_zonal_object_density: table as s2s_zonal_u8 writes it, scale a HOST double (mpp^2 * 1e-6); per_mm2 double
+ *   [owners][Z] = (double)objects / ((double)tissue * scale), 0 where tissue == 0.
+ * s2s_zonal_bands: d2_bg, d2_fg int [B][H][W] as s2s_morph_edt writes them (to_foreground = 0 / 1; 16-byte aligned, out
+ *   4-byte aligned, S2S_ERR_ALIGN otherwise); edges2 a HOST array of n ints in 1..126, 0 <= E_i < 2^31 - 1, not
+ *   descending.  A pixel is foreground iff d2_bg > 0.  Foreground: byte = #{i : d2_bg > E_i}; background: byte = n + 1 +
+ *   #{i : d2_fg > E_i}; side 1 ("inside") writes 255 on the background, side 2 ("outside") 255 on the foreground, side 0
+ *   neither.  out: bytes [B][H][W], dense. */
+int s2s_zonal_u8(const void* img, long pitch, long img_stride, const void* zones, long zone_pitch, long zone_stride, int B,
+                 int band_top, int band_h, int H, int W, int num_zones, const float* od_table, const float* unmix,
+                 int white, int black, int pool, int reset, long* table, long* unzoned, void* stream);
+int s2s_zonal_f32(const float* img, const void* zones, long zone_pitch, long zone_stride, int B, int H, int W,
+                  int num_zones, const float* od_table, const float* unmix, int white, int black, int pool, int reset,
+                  long* table, long* unzoned, void* stream);
+int s2s_zonal_pair_u8(const void* a, long pitch_a, long img_a, const void* b, long pitch_b, long img_b, const void* zones,
+                      long zone_pitch, long zone_stride, int B, int band_top, int band_h, int H, int W, int num_zones,
+                      const float* od_table, const float* unmix, int white, int black, int stain, int pool, int reset,
+                      long* table, long* unzoned, void* stream);
+int s2s_zonal_pair_f32(const float* a, const float* b, const void* zones, long zone_pitch, long zone_stride, int B, int H,
+                       int W, int num_zones, const float* od_table, const float* unmix, int white, int black, int stain,
+                       int pool, int reset, long* table, long* unzoned, void* stream);
+int s2s_zonal_finalize(const long* table, const long* unzoned, long owners, int num_zones, int paired, double* out,
+                       void* stream);
+int s2s_zonal_object_overlap(const int* labels, const void* zones, long zone_pitch, long zone_stride, int B, int H, int W,
+                             int num_zones, int max_objects, int* overlap, int* area, int* count, void* stream);
+int s2s_zonal_object_assign(const int* overlap, const int* area, const int* count, int B, int num_zones, int max_objects,
+                            int* zone, long* zone_pixels, long* objects, long* object_pixels, void* stream);
+int s2s_zonal_object_density(const long* objects, const long* table, long owners, int num_zones, const double* scale,
+                             double* per_mm2, void* stream);
+int s2s_zonal_bands(const int* d2_bg, const int* d2_fg, int B, int H, int W, const int* edges2, int n, int side, void* out,
+                    void* stream);
+
 /* ---- stain object analysis: connected-component labelling (objects.hip) -----------
  * A sample is H x W <= 2^31 - 2 pixels and has an index space of its own: nothing joins two samples.  B <= 65535.
  * s2s_objects_words(B, H, W): the int32 words of scratch s2s_objects_label needs (parents, then chunk counts);

@@ -28,6 +28,8 @@ from .stain_quant import (region_stain_agreement, region_stain_map, stain_agreem
 from .stain_calibrate import (calibrate_thresholds, match_thresholds, region_stain_histogram,
                               region_stain_pair_histogram, stain_histogram, stain_pair_histogram, stain_thresholds,
                               thresholds_tuple)
+from .zonal import (distance_zones, object_zones, region_stain_zonal, region_stain_zonal_agreement, stain_zonal,
+                    stain_zonal_agreement, stain_zonal_objects)
 from .stain_norm import REFERENCE_HE, StainFit, fit_stains, normalize_region, stain_normalize
 from .objects import label_components, region_stain_objects, stain_object_agreement, stain_objects
 from .augment import (PairedAugmenter, paired_augment, sample_d4_params, sample_stain_jitter, stain_augment,
@@ -68,4 +70,6 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "render_classes", "render_heat", "compare_regions", "downsample_region", "render_region", "compose_panels",
            "default_palette", "colormap",
            "stain_histogram", "region_stain_histogram", "stain_thresholds", "calibrate_thresholds", "thresholds_tuple",
-           "stain_pair_histogram", "region_stain_pair_histogram", "match_thresholds"]
+           "stain_pair_histogram", "region_stain_pair_histogram", "match_thresholds",
+           "stain_zonal", "stain_zonal_agreement", "region_stain_zonal", "region_stain_zonal_agreement", "object_zones",
+           "stain_zonal_objects", "distance_zones"]
