@@ -108,6 +108,10 @@ int s2s_conv3x3_wgrad_nhwc(int dtype, const void* dy, int lddy, int Cout, const 
 int s2s_conv3x3_wgrad_phase(int dtype, const void* dy, int lddy, int Cout, const void* x0, int ld0, int c0,
                             const void* x1, int ld1, int c1, float* part, float* grad_oihw, int accumulate,
                             int B, int H, int W, int phases, void* stream);
+/* tests and A/B only: variant 0 = the product kernel, 1 = the bf16 loop it replaced (same bits) */
+int s2s_conv3x3_wgrad_phase_variant(int dtype, const void* dy, int lddy, int Cout, const void* x0, int ld0, int c0,
+                                    const void* x1, int ld1, int c1, float* part, float* grad_oihw, int accumulate,
+                                    int B, int H, int W, int phases, int variant, void* stream);
 
 /* ---- stem and head (conv_edge.hip) ----------------------------------------------------------------
  * stem: first conv of SharedEncoder.inc (shared_encoder.py:15,67), NCHW fp32 image (Cin <= 6: RGB, or RGB + the

@@ -252,7 +252,48 @@ __device__ __forceinline__ void dma16_asm(const void* gsrc, unsigned lds_dst) {
 // A workgroup accumulates all nine taps (one dY fragment feeds nine MFMAs).  (Rounds 2-3 also built the kernel rows over
 // three workgroups, over the three 4-wave teams of a 12-wave workgroup, a two-team pixel split and a 16x16x32-MFMA form:
 // all parity-green, all 8-18 % slower -- DESIGN.md section 3.2 -- and deleted in round 4.)
-template <int TH, int TW>
+// ROWAHEAD (the product path): the same sums in the same order per accumulator, scheduled differently.
+//   * operand DMAs are buffer_load_dwordx4 ... lds through one raw buffer resource per tensor (as conv3x3_stage_kernel):
+//     a tile-invariant 32-bit byte offset per lane, a wave-uniform scalar base per tile, ZERO FILL for an offset past
+//     num_records -- padding pixels, channel pieces past Cout / Cin and groups past the halo take the offset out of
+//     range, so there is no zero page, no 64-bit address per lane and no pointer select.  Border tiles (and the
+//     iteration with no next tile) differ from interior tiles only in that the offsets of outside lanes are forced out
+//     of range; their base moves into the lane offset so that a halo origin in front of the tensor never reaches the
+//     scalar.  A 32-channel DMA group that straddles the x0 | x1 boundary of a concatenated input (c0 % 32 != 0) is
+//     fetched by two EXEC-masked loads, one per resource (WgradMixed; every other workgroup issues one load per group).
+//   * the tile's 72 MFMAs run halo row by halo row: row r's three X fragments (column shifts 0, 1, 2) and tile row
+//     r's dY fragment feed acc[ty*3+s] += dY[r-ty] . X[r][s] for the valid ty, so per accumulator the products still
+//     arrive in ascending tile row.  Row r+1's fragments are read behind row r's MFMAs (two register sets), and the
+//     next tile's ten DMAs are issued one per MFMA behind the tile's first MFMAs instead of as a block in front of it.
+// ROWAHEAD = false is the loop this one replaced (tests and A/B only: s2s_conv3x3_wgrad_phase_variant).
+typedef int wg_i32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ wg_i32x4 wg_rsrc(const void* base, long bytes) {
+  const unsigned long long u = (unsigned long long)(uintptr_t)base;
+  return wg_i32x4{(int)(unsigned)u, (int)(unsigned)(u >> 32), (int)bytes, 0x00020000};
+}
+
+// one wave-instruction of LDS-DMA: lane l's 16 bytes at rs.base + soff + voff land at lds_dst + 16 l (zeros when voff is
+// past num_records).  From inline asm for the reason given at dma16_asm.
+__device__ __forceinline__ void dma16_buf(wg_i32x4 rs, unsigned voff, unsigned soff, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 2\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(voff), "s"(rs), "s"(soff), "s"(lds_dst) : "memory");
+}
+// the same for a group whose lanes read two tensors: lanes of `first` from rs0, the others from rs1
+__device__ __forceinline__ void dma16_buf2(wg_i32x4 rs0, unsigned soff0, wg_i32x4 rs1, unsigned soff1, unsigned long long first,
+                                           unsigned voff, unsigned lds_dst) {
+  unsigned keep;
+  unsigned long long save;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %8\n\ts_mov_b64 %1, exec\n\ts_and_b64 exec, %1, %7\n\ts_nop 2\n\t"
+               "buffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_andn2_b64 exec, %1, %7\n\ts_nop 2\n\t"
+               "buffer_load_dwordx4 %2, %5, %6 offen lds\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep), "=&s"(save)
+               : "v"(voff), "s"(rs0), "s"(soff0), "s"(rs1), "s"(soff1), "s"(first), "s"(lds_dst)
+               : "memory", "scc");
+}
+
+template <int TH, int TW, bool ROWAHEAD>
 __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_dma_kernel(WgradArgs a) {
   using T = bf16_t;
   constexpr int NW = 4, NT = 9;
@@ -296,6 +337,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_dma_kernel(WgradArgs a) 
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[t][j] = 0.f;
 
+  if constexpr (!ROWAHEAD) {
   // Per-lane, tile-invariant parts of the DMA source addresses (which pixel of the tile / halo, which tensor and
   // channel); per tile only a wave-uniform pixel base changes.  Interior tiles (the whole halo inside the image)
   // take a path with no per-lane bounds tests: the address arithmetic otherwise costs a third of the loop's issue
@@ -393,6 +435,164 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_dma_kernel(WgradArgs a) 
     __builtin_amdgcn_s_barrier();
     buf ^= 1;
   }
+  } else {
+  constexpr int NB = TW / 16, NSTEP = HR * NB;             // a k-step is (halo row, 16-pixel block)
+  constexpr int NDMA = DYG + XG;
+  constexpr int DH = NPX / 16, XH = XROWS / 16;            // DMA groups per 32-channel half
+  constexpr unsigned OOB = 0xffffff00u;
+  static_assert(TW % 16 == 0, "a k-step is 16 consecutive pixels of one halo row");
+  const int wv = wave & 3;
+  const long npix = (long)a.B * a.H * a.W;                 // (the launcher refuses tensors of 2 GiB and more)
+  const wg_i32x4 rs_dy = wg_rsrc(dy, ((npix - 1) * a.lddy + a.Cout) * 2);
+  const wg_i32x4 rs_x0 = wg_rsrc(x0, ((npix - 1) * a.ld0 + a.c0) * 2);
+  const wg_i32x4 rs_x1 = wg_rsrc(a.c1 ? x1 : x0, a.c1 ? ((npix - 1) * a.ld1 + a.c1) * 2 : 0);
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+
+  // Tile-invariant lane offsets in bytes: dY from the tile's first pixel, X from the halo's first pixel.
+  unsigned inv[NDMA];
+#pragma unroll
+  for (int j = 0; j < DYG; ++j) {
+    const int grp = wv + NW * j;
+    const int px = (grp % DH) * 16 + drow, co = co0 + (grp / DH) * 32 + dslot * 8;
+    const int py = px / TW, pxx = px - py * TW;
+    inv[j] = co < a.Cout ? (unsigned)(((py * a.W + pxx) * a.lddy + co) * 2) : OOB;
+  }
+#pragma unroll
+  for (int j = 0; j < XG; ++j) {
+    const int grp = wv + NW * j;
+    const int px = (grp % XH) * 16 + drow, ci = ci0 + (grp / XH) * 32 + dslot * 8;
+    const int hy = px / HW_, hx = px - hy * HW_;
+    unsigned v = OOB;
+    if (px < HALO) {
+      if (ci < a.c0) v = (unsigned)(((hy * a.W + hx) * a.ld0 + ci) * 2);
+      else if (ci < cin) v = (unsigned)(((hy * a.W + hx) * a.ld1 + (ci - a.c0)) * 2);
+    }
+    inv[DYG + j] = v;
+  }
+  // which tensor a 32-channel half reads (wave-uniform), and for a half that straddles c0 the lanes of x0
+  bool second[2], mixed = false;
+  unsigned long long first[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int c = ci0 + 32 * h;
+    second[h] = c >= a.c0;
+    mixed = mixed || (a.c1 > 0 && c < a.c0 && c + 32 > a.c0);
+    first[h] = __builtin_amdgcn_ballot_w64(c + dslot * 8 < a.c0);
+  }
+
+  unsigned vo[NDMA], so_dy = 0, so_x[2] = {0, 0};          // the offsets and scalar bases of the tile whose DMAs come next
+  auto prep = [&](int tile, bool valid) {
+    int bt = valid ? tile : 0;
+    const int tx = bt % a.tilesX; bt /= a.tilesX;
+    const int ty = bt % a.tilesY;
+    const int img = bt / a.tilesY;
+    const int y0 = ty * TH, xs = tx * TW;
+    const int pixbase = (img * a.H + y0) * a.W + xs;       // wave-uniform
+    const int xb = pixbase - a.W - 1;                      // the halo's first pixel; negative for the first tile
+    const bool interior = valid && y0 >= 1 && y0 + TH + 1 <= a.H && xs >= 1 && xs + TW + 1 <= a.W;
+    so_dy = (unsigned)(pixbase * a.lddy * 2);
+    if (interior) {
+      so_x[0] = (unsigned)(xb * a.ld0 * 2);
+      so_x[1] = (unsigned)(xb * a.ld1 * 2);
+#pragma unroll
+      for (int j = 0; j < NDMA; ++j) vo[j] = inv[j];
+    } else {
+      // border: outside lanes out of range; the halo base rides in the lane offset (an inside lane's sum is its
+      // offset in the tensor, so 32-bit wrap-around in between is harmless)
+      so_x[0] = 0; so_x[1] = 0;
+      const unsigned b0 = (unsigned)(xb * a.ld0 * 2), b1 = (unsigned)(xb * a.ld1 * 2);
+#pragma unroll
+      for (int j = 0; j < DYG; ++j) {
+        const int px = ((wv + NW * j) % DH) * 16 + drow;
+        const int py = px / TW, pxx = px - py * TW;
+        vo[j] = (valid && y0 + py < a.H && xs + pxx < a.W) ? inv[j] : OOB;
+      }
+#pragma unroll
+      for (int j = 0; j < XG; ++j) {
+        const int grp = wv + NW * j;
+        const int px = (grp % XH) * 16 + drow, ci = ci0 + (grp / XH) * 32 + dslot * 8;
+        const int hy = px / HW_, hx = px - hy * HW_;
+        const int gy = y0 - 1 + hy, gx = xs - 1 + hx;
+        const bool ok = valid && inv[DYG + j] != OOB && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+        vo[DYG + j] = ok ? inv[DYG + j] + (ci < a.c0 ? b0 : b1) : OOB;
+      }
+    }
+  };
+  auto dma = [&](int j, int tobuf, auto mixedc) {
+    const unsigned dstb = lds0 + tobuf * BUF;
+    if (j < DYG) {
+      dma16_buf(rs_dy, vo[j], so_dy, dstb + (wv + NW * j) * 1024);
+    } else {
+      const int grp = wv + NW * (j - DYG), h = grp / XH;
+      const unsigned dst = dstb + DY_BYTES + grp * 1024;
+      if constexpr (decltype(mixedc)::value) {
+        dma16_buf2(rs_x0, so_x[0], rs_x1, so_x[1], h ? first[1] : first[0], vo[j], dst);
+      } else {
+        const bool s = h ? second[1] : second[0];
+        dma16_buf(s ? rs_x1 : rs_x0, vo[j], s ? so_x[1] : so_x[0], dst);
+      }
+    }
+  };
+
+  auto run = [&](auto mixedc) {
+    int tile = zsplit;
+    int buf = 0;
+    prep(tile, true);
+#pragma unroll
+    for (int j = 0; j < NDMA; ++j) dma(j, 0, mixedc);
+    prep(tile + a.S, tile + a.S < a.ntiles);               // (the offsets of a tile are made while the one before it lands)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    for (; tile < a.ntiles; tile += a.S) {
+      const char* const Ahi = smem + buf * BUF + wco * (NPX * 64) + frag_off;
+      const char* const Bhi = smem + buf * BUF + DY_BYTES + wci * (XROWS * 64) + frag_off;
+      bf16x8 xf[NSTEP][3], df[TH * NB];
+      // fragment `it` of step k: 0..2 the X fragments of column shifts 0..2, 3 the dY fragment (tile rows only)
+      auto rd = [&](int k, int it) {
+        const int r = k / NB, b = k - r * NB;
+        if (it < 3) xf[k][it] = tr_frag(Bhi + (r * HW_ + b * 16 + it) * 64, 4 * 64);
+        else df[k] = tr_frag(Ahi + (r * TW + b * 16) * 64, 4 * 64);
+      };
+      rd(0, 0); rd(0, 1); rd(0, 2); rd(0, 3);              // the one exposed read of the tile
+      __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);   // (these reads, not the next step's, fill the first group)
+      int m = 0;                                        // MFMAs issued so far in this tile
+#pragma unroll
+      for (int k = 0; k < NSTEP; ++k) {
+        const int r = k / NB, b = k - r * NB;
+        const int nfr = k + 1 < NSTEP ? ((k + 1) / NB < TH ? 4 : 3) : 0;   // fragments of the step after this one
+        const int nm = 3 * ((r < 2 ? r : 2) - (r - TH + 1 > 0 ? r - TH + 1 : 0) + 1);   // MFMAs of this step
+        int i = 0;
+#pragma unroll
+        for (int ty = 2; ty >= 0; --ty) {                  // the oldest dY fragment first
+          if (r - ty < 0 || r - ty >= TH) continue;
+#pragma unroll
+          for (int s = 0; s < 3; ++s) {
+            acc[ty * 3 + s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df[(r - ty) * NB + b], xf[k][s], acc[ty * 3 + s], 0, 0, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            // behind it: one fragment of the next step (what is left of them behind the step's last MFMA) ...
+#pragma unroll
+            for (int it = i; it < nfr && (it == i || i == nm - 1); ++it) {
+              rd(k + 1, it);
+              __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+            }
+            // ... and one DMA of the next tile: the kernel has ONE tile in flight per CU, so a tile cannot take less
+            // than the loaded memory latency plus the delay of its last DMA -- they go out behind the first ten MFMAs
+            if (m < NDMA) dma(m, buf ^ 1, mixedc);
+            ++m; ++i;
+          }
+        }
+      }
+      // every MFMA (hence every LDS read of this buffer) is issued before the barrier: the next iteration's DMAs
+      // overwrite this buffer's sibling, the ones after them this buffer
+      __builtin_amdgcn_sched_barrier(0);
+      prep(tile + 2 * a.S, tile + 2 * a.S < a.ntiles);     // while this tile's DMAs land
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      buf ^= 1;
+    }
+  };
+  if (mixed) run(std::true_type{}); else run(std::false_type{});
+  }
 
   const int r = lane & 31, h = lane >> 5;
   const int ci = ci0 + wci * 32 + r;
@@ -459,7 +659,7 @@ int launch_wgrad(WgradArgs& a, hipStream_t s) {
   return S2S_OK;
 }
 
-template <int TH, int TW>
+template <int TH, int TW, bool ROWAHEAD>
 int launch_wgrad_dma(WgradArgs& a, hipStream_t s) {
   constexpr int XROWS = ((TH + 2) * (TW + 2) + 31) / 32 * 32;
   constexpr int lds = 2 * (2 * TH * TW * 64 + 2 * XROWS * 64);
@@ -467,7 +667,13 @@ int launch_wgrad_dma(WgradArgs& a, hipStream_t s) {
   a.tilesX = cdiv(a.W, TW);
   a.ntiles = a.B * a.tilesY * a.tilesX;
   if (a.S > a.ntiles) return S2S_ERR_SHAPE;
-  auto kern = conv3x3_wgrad_dma_kernel<TH, TW>;
+  if (ROWAHEAD) {   // 32-bit byte offsets and num_records: every operand (as strided) stays below 2 GiB
+    const long npix = (long)a.B * a.H * a.W, lim = 0x7fffffffL;
+    if (((npix - 1) * a.lddy + a.Cout) * 2 > lim || ((npix - 1) * a.ld0 + a.c0) * 2 > lim ||
+        (a.c1 && ((npix - 1) * a.ld1 + a.c1) * 2 > lim))
+      return S2S_ERR_SHAPE;
+  }
+  auto kern = conv3x3_wgrad_dma_kernel<TH, TW, ROWAHEAD>;
   static unsigned long long attr_devs = 0;   // hipFuncSetAttribute is per device
   if (int rc = s2s_allow_dyn_lds(reinterpret_cast<const void*>(kern), lds, &attr_devs)) return rc;
   dim3 grid(cdiv(a.c0 + a.c1, 64), cdiv(a.Cout, 64), a.S);   // (a.xcd: set by the caller from conv3x3_wgrad_plan)
@@ -1258,11 +1464,12 @@ extern "C" int s2s_conv3x3_wgrad_plan(int dtype, int B, int H, int W, int Cin, i
 
 // phases: 1 = the split MFMA kernel (partial slabs into `part`), 2 = the fold of the slabs into the OIHW gradient,
 // 3 = both.  Two calls with phases 1 and 2 equal one call with 3; a profiler uses them to time the two kernels apart.
-extern "C" int s2s_conv3x3_wgrad_phase(int dtype, const void* dy, int lddy, int Cout, const void* x0, int ld0, int c0,
-                                       const void* x1, int ld1, int c1, float* part, float* grad_oihw,
-                                       int accumulate, int B, int H, int W, int phases, void* stream) {
+// variant (bf16 only; tests and A/B): 0 = the product kernel, 1 = the loop it replaced (conv3x3_wgrad_dma_kernel<.., false>)
+extern "C" int s2s_conv3x3_wgrad_phase_variant(int dtype, const void* dy, int lddy, int Cout, const void* x0, int ld0, int c0,
+                                               const void* x1, int ld1, int c1, float* part, float* grad_oihw,
+                                               int accumulate, int B, int H, int W, int phases, int variant, void* stream) {
   if (!dy || !x0 || !part || !grad_oihw) return S2S_ERR_NULL;
-  if (phases < 1 || phases > 3) return S2S_ERR_SHAPE;
+  if (phases < 1 || phases > 3 || variant < 0 || variant > 1) return S2S_ERR_SHAPE;
   if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || c0 <= 0 || c1 < 0) return S2S_ERR_SHAPE;
   if ((Cout % 8) || (c0 % 8) || (c1 % 8) || (lddy % 8) || (ld0 % 8) || (ld1 % 8) || (c1 > 0 && !x1)) return S2S_ERR_SHAPE;
   if (((uintptr_t)dy & 15) || ((uintptr_t)x0 & 15) || ((uintptr_t)x1 & 15)) return S2S_ERR_ALIGN;
@@ -1277,7 +1484,7 @@ extern "C" int s2s_conv3x3_wgrad_phase(int dtype, const void* dy, int lddy, int 
   hipStream_t s = static_cast<hipStream_t>(stream);
   int rc = S2S_OK;
   if (!(phases & 1)) { if (a.S > plan.tiles) return S2S_ERR_SHAPE; }
-  else if (plan.kernel == 0) rc = launch_wgrad_dma<8, 16>(a, s);
+  else if (plan.kernel == 0) rc = variant ? launch_wgrad_dma<8, 16, false>(a, s) : launch_wgrad_dma<8, 16, true>(a, s);
   else rc = launch_wgrad<float, 8, 16>(a, s);
   if (rc != S2S_OK || !(phases & 2)) return rc;
   const long n = (long)Cout * (c0 + c1);
@@ -1289,6 +1496,13 @@ extern "C" int s2s_conv3x3_wgrad_phase(int dtype, const void* dy, int lddy, int 
                        a.S, Cout, c0 + c1, accumulate);
   S2S_LAUNCH_CHECK();
   return S2S_OK;
+}
+
+extern "C" int s2s_conv3x3_wgrad_phase(int dtype, const void* dy, int lddy, int Cout, const void* x0, int ld0, int c0,
+                                       const void* x1, int ld1, int c1, float* part, float* grad_oihw,
+                                       int accumulate, int B, int H, int W, int phases, void* stream) {
+  return s2s_conv3x3_wgrad_phase_variant(dtype, dy, lddy, Cout, x0, ld0, c0, x1, ld1, c1, part, grad_oihw, accumulate, B, H, W,
+                                         phases, 0, stream);
 }
 
 extern "C" int s2s_conv3x3_wgrad_nhwc(int dtype, const void* dy, int lddy, int Cout, const void* x0, int ld0, int c0,

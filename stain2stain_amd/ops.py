@@ -363,7 +363,10 @@ def conv3x3_plan(dtype: torch.dtype, B: int, H: int, W: int, c0: int, c1: int, c
 
 
 def conv3x3_wgrad(dy: torch.Tensor, x0: torch.Tensor, x1: Optional[torch.Tensor], grad_oihw: torch.Tensor,
-                  accumulate: bool = False) -> None:
+                  accumulate: bool = False, _reference: bool = False, _phases: int = 3,
+                  _part: Optional[torch.Tensor] = None) -> None:
+    """``_reference`` (tests only): the bf16 tile loop that the row-ahead loop replaced; same bits.  ``_phases`` /
+    ``_part`` (tests only): 1 = the split kernel alone into the caller's slabs, 2 = the fold alone, 3 = both."""
     B, H, W, cout = dy.shape
     c0 = x0.shape[3]
     dt = _dt(dy)
@@ -378,6 +381,16 @@ def conv3x3_wgrad(dy: torch.Tensor, x0: torch.Tensor, x1: Optional[torch.Tensor]
     if tuple(grad_oihw.shape) != (cout, c0 + c1, 3, 3):
         raise RuntimeError("stain2stain_amd: conv3x3_wgrad gradient buffer has the wrong shape")
     s = _L().s2s_conv3x3_wgrad_splits(dt, B, H, W, c0 + c1, cout)
+    if _reference or _phases != 3 or _part is not None:
+        if _part is None:
+            _part = _workspace(dy.device, s * 9 * cout * (c0 + c1), "wgrad")
+        elif _part.dtype != torch.float32 or _part.numel() < s * 9 * cout * (c0 + c1) or not _part.is_contiguous():
+            raise RuntimeError("stain2stain_amd: conv3x3_wgrad slab buffer is too small")
+        rc = _L().s2s_conv3x3_wgrad_phase_variant(dt, pdy, lddy, cout, p0, ld0, c0, p1, ld1, c1, _f32(_part),
+                                                  _f32(grad_oihw), int(accumulate), B, H, W, _phases, int(_reference),
+                                                  _stream())
+        _native.check(rc, "conv3x3_wgrad")
+        return
     part = _workspace(dy.device, s * 9 * cout * (c0 + c1), "wgrad")
     if _PROFILE is not None and (_PROFILE_ONLY is None or "conv3x3_wgrad_mfma" in _PROFILE_ONLY):
         # event-bracketed: the split MFMA kernel and the fold of its slabs as two launches, each timed on its own
