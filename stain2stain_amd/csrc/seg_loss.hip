@@ -66,9 +66,13 @@ __global__ void seg_loss_bwd_kernel(const float* __restrict__ z, const float* __
   const float invn = (float)(1.0 / (double)n);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const float zi = z[i], gi = g[i];
-    const float p = 1.f / (1.f + expf(-zi));
-    const float ddice = -(gi * a - b) * p * (1.f - p);
-    const float dbce = (p - gi) * invn;
+    // p and 1 - p from e = exp(-|z|) without a subtraction: 1.f - p is 0 from z = 17 on, and p - g with it wherever a
+    // saturated logit has the right label, while the gradient there is e times its factor, not 0
+    const float e = expf(-fabsf(zi));
+    const float big = 1.f / (1.f + e), small = e * big;
+    const float p = zi >= 0.f ? big : small, q = zi >= 0.f ? small : big;
+    const float ddice = -(gi * a - b) * (big * small);
+    const float dbce = (zi >= 0.f ? (1.f - gi) - q : p - gi) * invn;
     dz[i] = scale * (dice_w * ddice + (1.f - dice_w) * dbce);
   }
 }

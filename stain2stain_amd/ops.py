@@ -843,6 +843,10 @@ def mse_loss(v: torch.Tensor, u: torch.Tensor, want_grad: bool = True, grad_scal
 def seg_loss(z: torch.Tensor, g: torch.Tensor, smooth: float = 1.0, dice_weight: float = 0.5, want_grad: bool = True,
              grad_scale: float = 1.0):
     """Dice + BCE-with-logits on a logit map; returns (out[3] = seg, dice, bce; dz or None)."""
+    if g.dim() == 3 and z.dim() == 4:
+        g = g.unsqueeze(1)
+    if tuple(g.shape) != tuple(z.shape):
+        raise RuntimeError(f"stain2stain_amd: mask shape {tuple(g.shape)} does not match logits {tuple(z.shape)}")
     z = z.contiguous()
     g = g.to(torch.float32).contiguous()
     out = torch.empty((3,), dtype=torch.float32, device=z.device)
@@ -861,6 +865,8 @@ def seg_loss_multiclass(z: torch.Tensor, target: torch.Tensor, ignore_index: int
     outside [0, C) (F.one_hot raises there) at the cost of one host sync."""
     if z.dim() != 4 or target.dim() != 3 or target.shape != (z.shape[0], z.shape[2], z.shape[3]):
         raise RuntimeError("stain2stain_amd: seg_loss_multiclass wants logits [B,C,H,W] and target [B,H,W]")
+    if target.device != z.device:
+        raise RuntimeError("stain2stain_amd: logits and target are on different devices")
     B, C, H, W = z.shape
     z = z.contiguous()
     target = target.to(torch.int64).contiguous()
@@ -1022,20 +1028,36 @@ def charbonnier_roi(pred: torch.Tensor, truth: torch.Tensor, mask: torch.Tensor,
     return out
 
 
+def _labels(y: torch.Tensor, B: int, like: torch.Tensor, what: str) -> int:
+    """The pointer of a class-index vector the kernels read as int64[B] on ``like``'s device."""
+    if tuple(y.shape) != (B,):
+        raise RuntimeError(f"stain2stain_amd: {what} wants one class index per sample, got y {tuple(y.shape)} for B = {B}")
+    if y.dtype != torch.int64 or y.device != like.device or not y.is_contiguous():
+        raise RuntimeError(f"stain2stain_amd: {what} wants y as a contiguous int64 tensor on {like.device}, "
+                           f"got {y.dtype} on {y.device}")
+    return y.data_ptr()
+
+
 def class_embed_add(temb: torch.Tensor, table: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    if temb.dim() != 2 or table.dim() != 2:
+        raise RuntimeError("stain2stain_amd: class_embed_add wants temb [B, dim] and table [classes, dim]")
     B, dim = temb.shape
-    if table.shape[1] != dim or y.shape != (B,):
+    if table.shape[1] != dim:
         raise RuntimeError("stain2stain_amd: class_embed_add shape mismatch")
+    yp = _labels(y, B, temb, "class_embed_add")
     out = torch.empty_like(temb)
-    _native.check(_L().s2s_class_embed_add(_f32(temb.contiguous()), _f32(table), y.data_ptr(), _f32(out), B, dim,
+    _native.check(_L().s2s_class_embed_add(_f32(temb.contiguous()), _f32(table), yp, _f32(out), B, dim,
                                            _stream()), "class_embed_add")
     return out
 
 
 def class_embed_bwd(dout: torch.Tensor, y: torch.Tensor, num_classes: int) -> torch.Tensor:
+    if dout.dim() != 2:
+        raise RuntimeError("stain2stain_amd: class_embed_bwd wants dout [B, dim]")
     B, dim = dout.shape
+    yp = _labels(y, B, dout, "class_embed_bwd")
     dtable = torch.empty((num_classes, dim), dtype=torch.float32, device=dout.device)
-    _native.check(_L().s2s_class_embed_bwd(_f32(dout.contiguous()), y.data_ptr(), _f32(dtable), 0, B, dim,
+    _native.check(_L().s2s_class_embed_bwd(_f32(dout.contiguous()), yp, _f32(dtable), 0, B, dim,
                                            num_classes, _stream()), "class_embed_bwd")
     return dtable
 
