@@ -1174,6 +1174,54 @@ int s2s_p2p_act_bwd_blocks(long npix, int C);
 int s2s_p2p_act_bwd(int dtype, const void* g, int ldg, const void* g2, int ldg2, const void* a, int lda, float slope,
                     void* dz, int lddz, float* work, float* dbias, int accumulate, long npix, int C, void* stream);
 
+/* ---- stain background subtraction: grey opening and top-hat (grey_morph.hip) ----------
+ * Grey images are uint8 (dtype 0) or int16 (dtype 1) [B][H][.] with pitch and img_stride in ELEMENTS; results are dense
+ *   [B][H][W].  H, W <= 32767 and B <= 65535; the radius is at most MAX_RADIUS = 128 and smooth at most 16; anything
+ *   beyond is refused with the shape status before any launch.  Nothing lies outside the image: a minimum or maximum
+ *   runs over the in-image pixels of the footprint only (scipy.ndimage.grey_erosion(mode="constant", cval=type max) and
+ *   grey_dilation(cval=type min)).
+ * Footprints: 0 disc, {(dy, dx): dy^2 + dx^2 <= size}, size = floor(radius^2) <= 128^2 (the r2 of s2s_morph_threshold);
+ *   1 square, |dy|, |dx| <= size = floor(radius) <= 128.
+ * Operations: 0 erode (min), 1 dilate (max), 2 open = dilate(erode), 3 close = erode(dilate), 4 tophat = x - open(x),
+ *   5 bothat = close(x) - x; the differences are formed in 32 bits and saturated to the dtype.
+ * s2s_grey_words: the int32 words of scratch s2s_grey_morph needs (the span tables of one pass and one intermediate
+ *   plane); negative: a status code.  scratch must be 2-byte aligned.
+ * s2s_grey_morph: 1 + levels launches per erosion or dilation (levels = floor(log2(min(2 floor(radius) + 1, W))) + 1),
+ *   twice that for the four compound operations.  Every element of out is written.
+ * s2s_grey_box_mean: int16 values >= 0, dense: out = (2 sum + n) / (2 n) in integer division, sum and n over the
+ *   in-image pixels of the (2 smooth + 1)^2 window; smooth = 0 copies.
+ * s2s_grey_bins_u8 / _f32: images, od_table, unmix (nine floats are read), white, black as in stain threshold
+ *   calibration; bins short [B][rows][W] = bin(c_stain) = clamp(ceil(c * 1024) - 1, 0, 4095) of EVERY pixel (no tissue
+ *   gate), with the fp32 operations of s2s_stain_hist_*; tissue (bytes, may be null) = the tissue rule, 0 / 1.  The uint8
+ *   buffers hold `rows` rows of B images (pitch, img_stride in bytes).
+ * s2s_grey_corrected: t = max(bins - bg, 0) (bg null: t = bins) over rows [row0, row0 + nrows) of dense short
+ *   [B][rows][W] buffers (the other rows are a band's halo: read by the morphology, not counted here).  An owner is a
+ *   sample, or the batch (pool != 0).  counts long [owners][3] += tissue pixels, tissue pixels with t >= j (j in
+ *   1..4095), the sum of t over tissue; hist long [owners][3][4096]: row `stain` += tissue pixels by t.  64-bit integer
+ *   atomics; reset != 0 zeroes all of counts and hist first, in a launch of its own.  mask (bytes, may be null): bit 0
+ *   positive, bit 1 tissue; corrected (short, may be null): t; both [B][nrows][W] with out_img elements per sample.
+ *   A launch whose workgroups would count 2^32 pixels or more each is refused.
+ * s2s_grey_corrected_finalize: out double [owners][2] = positive / max(tissue, 1), sum_t / max(tissue, 1).
+ * s2s_grey_pair: both long [B] = the pixels with bit 0 set in both of two dense byte masks [B][H][W] (written).
+ * s2s_grey_pair_finalize: counts_a / counts_b as s2s_grey_corrected leaves them for B owners: out double [B][5] = the
+ *   two burdens, their absolute difference, Dice = 2 both / (positive_a + positive_b) and IoU, both 1 when both masks
+ *   are empty. */
+long s2s_grey_words(int B, int H, int W, int footprint, int size);
+int s2s_grey_morph(const void* src, int dtype, long pitch, long img_stride, int B, int H, int W, int op, int footprint,
+                   int size, int* scratch, void* out, void* stream);
+int s2s_grey_box_mean(const short* src, int B, int H, int W, int smooth, short* out, void* stream);
+int s2s_grey_bins_u8(const void* img, long pitch, long img_stride, int B, int rows, int W, const float* od_table,
+                     const float* unmix, int white, int black, int stain, short* bins, void* tissue, void* stream);
+int s2s_grey_bins_f32(const float* img, int B, int H, int W, const float* od_table, const float* unmix, int white,
+                      int black, int stain, short* bins, void* tissue, void* stream);
+int s2s_grey_corrected(const short* bins, const short* bg, const void* tissue, int B, int rows, int W, int row0,
+                       int nrows, int j, int stain, int pool, int reset, long* counts, long* hist, void* mask,
+                       short* corrected, long out_img, void* stream);
+int s2s_grey_corrected_finalize(const long* counts, long owners, double* out, void* stream);
+int s2s_grey_pair(const void* mask_a, const void* mask_b, int B, int H, int W, long* both, void* stream);
+int s2s_grey_pair_finalize(const long* counts_a, const long* counts_b, const long* both, int B, double* out,
+                           void* stream);
+
 /* ---- streams (runtime.hip) -------------------------------------------------------------------------
  * A HIP stream confined to the compute units whose bits are set in mask_words (bit i of word i/32 = CU i, as
  * hipExtStreamCreateWithCUMask numbers them); *out_stream receives the hipStream_t.  Used for the weight-gradient side

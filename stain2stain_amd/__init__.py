@@ -30,6 +30,9 @@ from .stain_calibrate import (calibrate_thresholds, match_thresholds, region_sta
                               thresholds_tuple)
 from .zonal import (distance_zones, object_zones, region_stain_zonal, region_stain_zonal_agreement, stain_zonal,
                     stain_zonal_agreement, stain_zonal_objects)
+from .background import (concentration_bins, grey_morphology, region_stain_quantify_corrected,
+                         stain_agreement_corrected, stain_background, stain_objects_corrected,
+                         stain_quantify_corrected)
 from .stain_norm import REFERENCE_HE, StainFit, fit_stains, normalize_region, stain_normalize
 from .objects import label_components, region_stain_objects, stain_object_agreement, stain_objects
 from .augment import (PairedAugmenter, paired_augment, sample_d4_params, sample_stain_jitter, stain_augment,
@@ -72,4 +75,6 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "stain_histogram", "region_stain_histogram", "stain_thresholds", "calibrate_thresholds", "thresholds_tuple",
            "stain_pair_histogram", "region_stain_pair_histogram", "match_thresholds",
            "stain_zonal", "stain_zonal_agreement", "region_stain_zonal", "region_stain_zonal_agreement", "object_zones",
-           "stain_zonal_objects", "distance_zones"]
+           "stain_zonal_objects", "distance_zones",
+           "grey_morphology", "concentration_bins", "stain_background", "stain_quantify_corrected",
+           "stain_objects_corrected", "stain_agreement_corrected", "region_stain_quantify_corrected"]
