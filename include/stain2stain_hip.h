@@ -671,6 +671,17 @@ int s2s_zonal_bands(const int* d2_bg, const int* d2_fg, int B, int H, int W, con
  *   tab_area int [B][M], tab_bbox int [B][M][4] (y0, x0, y1, x1, end-exclusive) and tab_sums long [B][M][2] (sum of y,
  *   sum of x) are written, the other rows are not touched (the caller zeroes the tables).  max_objects == 0: no table,
  *   the three pointers are ignored.  Nine launches, no host synchronisation.
+ * s2s_objects_label_seeded: s2s_objects_label of the components SELECTED by a marker.  marker
+ *   bytes [B][H][.] (marker_pitch, marker_img_stride in bytes; it may be the mask's buffer under other bits): a seed is a
+ *   foreground pixel with (marker byte & seed_bits) != 0, seed_bits in 1..255.  seeds(component) = its seeds; a component
+ *   is selected iff (seeds >= min_seed) != invert, min_seed >= 1, invert 0 or 1.  The pixels of the components not
+ *   selected are background for everything s2s_objects_label computes (min_area, numbering, statistics and tables then
+ *   work on the selected ones as above).  out_mask (bytes [B][H][.], out_pitch / out_img_stride in bytes, may be null):
+ *   every byte is written, 1 on the pixels of the selected components (before the area filter) and 0 elsewhere, | (mask
+ *   byte & 2) when fg_bits == 1 (the stain-mask convention: bit 0 positive, bit 1 tissue).  candidates int [B] = the
+ *   components of the mask, seeded int [B] = those with seeds >= min_seed (before invert and the area filter),
+ *   seed_pixels long [B] = the seeds; all three are written (zeroed by a launch of this call).  scratch: the words of
+ *   s2s_objects_words.  Thirteen launches, no host synchronisation.
  * s2s_objects_centroid: centroid float [B][M][2] = float((double)sum / area) for rows < count, 0 beyond.
  * s2s_objects_hits: hits int [B][2] = the objects of labels_pred that share a pixel with an object of labels_target, and
  *   the other way round (per-object bit flags in scratch set by atomicOr, then counted).  Both are written.
@@ -684,6 +695,12 @@ long s2s_objects_hit_words(int B, int H, int W);
 int s2s_objects_label(const void* mask, long pitch, long img_stride, int fg_bits, int B, int H, int W, int connectivity,
                       int min_area, int max_objects, int* scratch, int* labels, int* count, long* kept_pixels,
                       int* largest, long* size_hist, int* tab_area, int* tab_bbox, long* tab_sums, void* stream);
+int s2s_objects_label_seeded(const void* mask, long pitch, long img_stride, int fg_bits, const void* marker,
+                             long marker_pitch, long marker_img_stride, int seed_bits, int min_seed, int invert, int B,
+                             int H, int W, int connectivity, int min_area, int max_objects, int* scratch, int* labels,
+                             int* count, long* kept_pixels, int* largest, long* size_hist, int* tab_area, int* tab_bbox,
+                             long* tab_sums, void* out_mask, long out_pitch, long out_img_stride, int* candidates,
+                             int* seeded, long* seed_pixels, void* stream);
 int s2s_objects_centroid(const int* count, const int* tab_area, const long* tab_sums, int B, int max_objects,
                          float* centroid, void* stream);
 int s2s_objects_hits(const int* labels_pred, const int* labels_target, int B, int H, int W, int* scratch, int* hits,
@@ -1221,6 +1238,21 @@ int s2s_grey_corrected_finalize(const long* counts, long owners, double* out, vo
 int s2s_grey_pair(const void* mask_a, const void* mask_b, int B, int H, int W, long* both, void* stream);
 int s2s_grey_pair_finalize(const long* counts_a, const long* counts_b, const long* both, int B, double* out,
                            void* stream);
+
+/* ---- hysteresis thresholding: the dual-threshold mask (hysteresis.hip) ------------------
+ * s2s_hyst_mask: t short [B][rows][W] on the 1/1024 OD grid (the bins of s2s_grey_bins_*, or the corrected t of
+ *   s2s_grey_corrected) and tissue bytes of the same layout (0 / not 0; null: every pixel is tissue), over rows
+ *   [row0, row0 + nrows) (the other rows are a band's halo).  0 <= j_low <= j_high <= 4095.  mask bytes [B][nrows][W]
+ *   with out_img elements per sample, every one written: bit 0 = tissue and t >= j_low (weak), bit 1 = tissue, bit 2 =
+ *   tissue and t >= j_high (strong).  An owner is a sample, or the batch (pool != 0).  counts long [owners][3] += the
+ *   tissue, weak and strong pixels (64-bit integer atomics, one set per workgroup); reset != 0 zeroes counts first, in a
+ *   launch of its own.  rows, W <= 32767, B <= 65535; a launch whose workgroups would count 2^32 pixels or more each is
+ *   refused.  The hysteresis mask is s2s_objects_label_seeded of this byte with fg_bits = 1, seed_bits = 4.
+ * s2s_hyst_finalize: positive long [owners], counts as s2s_hyst_mask leaves them: burden double [owners] =
+ *   positive / max(tissue, 1). */
+int s2s_hyst_mask(const short* t, const void* tissue, int B, int rows, int W, int row0, int nrows, int j_low, int j_high,
+                  int pool, int reset, long* counts, void* mask, long out_img, void* stream);
+int s2s_hyst_finalize(const long* positive, const long* counts, long owners, double* burden, void* stream);
 
 /* ---- streams (runtime.hip) -------------------------------------------------------------------------
  * A HIP stream confined to the compute units whose bits are set in mask_words (bit i of word i/32 = CU i, as

@@ -33,6 +33,9 @@ from .zonal import (distance_zones, object_zones, region_stain_zonal, region_sta
 from .background import (concentration_bins, grey_morphology, region_stain_quantify_corrected,
                          stain_agreement_corrected, stain_background, stain_objects_corrected,
                          stain_quantify_corrected)
+from .hysteresis import (clear_border, hysteresis_mask, hysteresis_thresholds, reconstruct_mask,
+                         region_stain_objects_hysteresis, select_components, stain_agreement_hysteresis,
+                         stain_objects_hysteresis)
 from .stain_norm import REFERENCE_HE, StainFit, fit_stains, normalize_region, stain_normalize
 from .objects import label_components, region_stain_objects, stain_object_agreement, stain_objects
 from .augment import (PairedAugmenter, paired_augment, sample_d4_params, sample_stain_jitter, stain_augment,
@@ -77,4 +80,6 @@ __all__ = ["SharedEncoder", "FlowMatchingDecoder", "SegmentationDecoder", "TimeE
            "stain_zonal", "stain_zonal_agreement", "region_stain_zonal", "region_stain_zonal_agreement", "object_zones",
            "stain_zonal_objects", "distance_zones",
            "grey_morphology", "concentration_bins", "stain_background", "stain_quantify_corrected",
-           "stain_objects_corrected", "stain_agreement_corrected", "region_stain_quantify_corrected"]
+           "stain_objects_corrected", "stain_agreement_corrected", "region_stain_quantify_corrected",
+           "select_components", "reconstruct_mask", "clear_border", "hysteresis_mask", "stain_objects_hysteresis",
+           "stain_agreement_hysteresis", "region_stain_objects_hysteresis", "hysteresis_thresholds"]

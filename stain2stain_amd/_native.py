@@ -20,7 +20,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "stain2stain_hip.h")
 SOURCES = ["conv3x3_mfma.hip", "conv3x3_wgrad_mfma.hip", "conv_small.hip", "conv_edge.hip", "norm_act.hip", "resample.hip",
            "flow.hip", "ode.hip", "optim.hip", "input_pipeline.hip", "seg_loss.hip", "eval_metrics.hip", "loss_variants.hip", "instnorm.hip", "pix2pix.hip",
            "region.hip", "image_metrics.hip", "stain_quant.hip", "stain_norm.hip", "objects.hip", "augment.hip", "registration.hip", "warp.hip", "qc.hip", "morphology.hip", "runtime.hip", "object_features.hip", "split.hip", "rigid.hip", "render.hip",
-           "stain_calibrate.hip", "zonal.hip", "grey_morph.hip"]
+           "stain_calibrate.hip", "zonal.hip", "grey_morph.hip", "hysteresis.hip"]
 
 HEADERS = ["common.h", "objects_number.h"]     # csrc headers: a change to one rebuilds every object
 

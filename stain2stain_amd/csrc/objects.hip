@@ -7,6 +7,11 @@
 //                         first pixel, the numbering of scipy.ndimage.label), per-sample count, kept pixels, largest area
 //                         and a log2 size histogram, and optionally a table (area, bounding box, coordinate sums) of the
 //                         objects numbered <= max_objects
+//   s2s_objects_label_seeded  the same, of the components selected by what they contain: a component is kept iff
+//                         (marked foreground pixels >= min_seed) != invert (binary reconstruction, hysteresis: DESIGN.md
+//                         3.37).  Three more passes between flatten and the numbering stage, the parent array as the
+//                         per-root counter: zero, seed (parent[root] += marked pixels, one atomic per wave and distinct
+//                         root), gate (labels = -1 on the components not selected, the selected mask, the root counts)
 //   s2s_objects_centroid  the table's coordinate sums -> fp32 centroids; rows at or beyond count are zeroed
 //   s2s_objects_hits      two label images -> how many objects of each touch an object of the other
 //   s2s_objects_scores    counts and hits -> recall, precision, F1, |count difference|
@@ -203,6 +208,118 @@ __global__ __launch_bounds__(256) void ob_area_kernel(const int* __restrict__ la
     if (lane == leader) atomicAdd(a + lk, __popcll(same));
     todo &= ~same;
   }
+}
+
+// ---- seeded selection (s2s_objects_label_seeded): between flatten and the numbering stage ------------------
+struct ObSeed {
+  const unsigned char* marker;   // [B][H][.], a seed iff (byte & bits) != 0 on a foreground pixel
+  long pitch, img;
+  int bits;
+  int min_seed, invert;
+  const unsigned char* mask;     // the labelled mask (for bit 1 of out)
+  long mask_pitch, mask_img;
+  int keep_tissue;               // out keeps bit 1 of the mask byte (the stain-mask convention)
+  unsigned char* out;            // [B][H][.] or null
+  long out_pitch, out_img;
+  int W;
+};
+
+__global__ __launch_bounds__(256) void ob_seed_zero_kernel(int B, int* __restrict__ candidates, int* __restrict__ seeded,
+                                                           long long* __restrict__ seed_pixels) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= B) return;
+  candidates[n] = 0;
+  seeded[n] = 0;
+  seed_pixels[n] = 0;
+}
+
+constexpr int OB_SEED_PER = 8;               // pixels a thread of the seed and gate passes: a workgroup covers 2048
+
+// seeds[root] += the marked foreground pixels, one integer atomic per wave and distinct root (as ob_area_kernel); a wave
+// whose 64 pixels all hold one root keeps that count over its rounds and adds it once.  seed_pixels[n] += their number,
+// one atomic per workgroup (every workgroup of a sample adds to ONE address: with 256 pixels a workgroup these atomics,
+// not the traffic, were the whole cost of the pass).  seeds is zero at the roots (ob_zero_kernel).
+__global__ __launch_bounds__(256) void ob_seed_kernel(const int* __restrict__ labels, long hw, const ObSeed k, int* seeds,
+                                                      long long* seed_pixels) {
+  __shared__ int s_n;
+  const int lane = threadIdx.x & 63, n = blockIdx.y;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  int* a = seeds + (long)n * hw;
+  int mine = 0, held_key = -1, held = 0;                // (held_*: wave-uniform)
+#pragma unroll 2
+  for (int j = 0; j < OB_SEED_PER; ++j) {
+    const long i = ((long)blockIdx.x * OB_SEED_PER + j) * 256 + threadIdx.x;
+    int key = -1;
+    if (i < hw) {
+      const int r = labels[(long)n * hw + i];
+      if (r >= 0) {
+        const unsigned y = (unsigned)i / (unsigned)k.W, x = (unsigned)i - y * (unsigned)k.W;
+        if (k.marker[(long)n * k.img + (long)y * k.pitch + x] & k.bits) key = r;
+      }
+    }
+    unsigned long long todo = __ballot(key >= 0);
+    if (lane == 0) mine += __popcll(todo);
+    while (todo) {                                      // wave-uniform
+      const int leader = __ffsll((long long)todo) - 1;
+      const int lk = __shfl(key, leader, 64);
+      const unsigned long long same = __ballot(key == lk);
+      if (lk == held_key) {
+        held += __popcll(same);
+      } else {
+        if (held && lane == 0) atomicAdd(a + held_key, held);
+        held_key = lk;
+        held = __popcll(same);
+      }
+      todo &= ~same;
+    }
+  }
+  if (held && lane == 0) atomicAdd(a + held_key, held);
+  if (lane == 0 && mine) atomicAdd(&s_n, mine);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_n) atomicAdd((unsigned long long*)seed_pixels + n, (unsigned long long)s_n);
+}
+
+// labels[i] = -1 on the pixels of the components that are not selected; out = 1 on the selected pixels (| bit 1 of the
+// mask byte); candidates / seeded: the roots, one atomic set per workgroup.  seeds is only read.
+__global__ __launch_bounds__(256) void ob_gate_kernel(int* __restrict__ labels, const int* __restrict__ seeds, long hw,
+                                                      const ObSeed k, int* candidates, int* seeded) {
+  __shared__ int s_c[2];
+  const int lane = threadIdx.x & 63, n = blockIdx.y;
+  if (threadIdx.x < 2) s_c[threadIdx.x] = 0;
+  __syncthreads();
+  int nroot = 0, nhas = 0;                              // (lane 0 of each wave counts)
+#pragma unroll 2
+  for (int j = 0; j < OB_SEED_PER; ++j) {
+    const long i = ((long)blockIdx.x * OB_SEED_PER + j) * 256 + threadIdx.x;
+    bool root = false, has = false;
+    if (i < hw) {
+      const long o = (long)n * hw + i;
+      const int r = labels[o];
+      bool sel = false;
+      if (r >= 0) {
+        has = seeds[(long)n * hw + r] >= k.min_seed;
+        sel = has != (k.invert != 0);
+        root = r == (int)i;
+        if (!sel) labels[o] = -1;
+      }
+      if (k.out) {
+        const unsigned y = (unsigned)i / (unsigned)k.W, x = (unsigned)i - y * (unsigned)k.W;
+        unsigned char v = sel ? 1 : 0;
+        if (k.keep_tissue) v |= k.mask[(long)n * k.mask_img + (long)y * k.mask_pitch + x] & 2;
+        k.out[(long)n * k.out_img + (long)y * k.out_pitch + x] = v;
+      }
+    }
+    nroot += __popcll(__ballot(root));
+    nhas += __popcll(__ballot(root && has));
+  }
+  if (lane == 0) {
+    if (nroot) atomicAdd(&s_c[0], nroot);
+    if (nhas) atomicAdd(&s_c[1], nhas);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && s_c[0]) atomicAdd(candidates + n, s_c[0]);
+  if (threadIdx.x == 1 && s_c[1]) atomicAdd(seeded + n, s_c[1]);
 }
 
 // exclusive scan of one int per thread over the 256 threads; returns the thread's prefix, *total = the sum
@@ -443,6 +560,20 @@ bool ob_shape_ok(int B, int H, int W) {
 }
 long ob_flag_words(long hw) { return (hw / 2 + 2 + 31) / 32; }
 
+// local, merge, flatten: labels[i] = the first raster pixel of i's component, -1 on background
+void ob_roots(const ObMask& k, int B, int conn8, int* parent, int* labels, hipStream_t s) {
+  const int H = k.H, W = k.W;
+  const long hw = (long)H * W;
+  const int tiles_y = cdiv(H, OT_H), tiles_x = cdiv(W, OT_W);
+  const long tiles = (long)tiles_y * tiles_x, pix_blocks = (hw + 255) / 256;
+  hipLaunchKernelGGL(ob_local_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(256), 0, s, k, tiles_x, conn8, parent);
+  const long n_h = (long)(tiles_y - 1) * W, n_v = (long)(tiles_x - 1) * H;
+  if (n_h + n_v > 0)
+    hipLaunchKernelGGL(ob_merge_kernel, dim3((unsigned)((n_h + n_v + 255) / 256), (unsigned)B), dim3(256), 0, s, k, n_h,
+                       n_v, conn8, parent);
+  hipLaunchKernelGGL(ob_flatten_kernel, dim3((unsigned)pix_blocks, (unsigned)B), dim3(256), 0, s, parent, hw, labels);
+}
+
 }  // namespace
 
 // ---- the numbering stage (objects_number.h): zero, area, count, scan, number, relabel -----------------------------------
@@ -488,19 +619,65 @@ extern "C" int s2s_objects_label(const void* mask, long pitch, long img_stride, 
   static_assert(sizeof(long) == sizeof(long long), "int64 counts");
   hipStream_t s = (hipStream_t)stream;
   const long hw = (long)H * W;
-  const int tiles_y = cdiv(H, OT_H), tiles_x = cdiv(W, OT_W);
-  const long tiles = (long)tiles_y * tiles_x, pix_blocks = (hw + 255) / 256;
-  if (tiles > 0x7fffffffL) return S2S_ERR_SHAPE;
+  if ((long)cdiv(H, OT_H) * cdiv(W, OT_W) > 0x7fffffffL) return S2S_ERR_SHAPE;
   int* parent = scratch;
   int* chunk = scratch + (long)B * hw;
   const ObMask k{(const unsigned char*)mask, pitch, img_stride, fg_bits, H, W};
-  const int conn8 = connectivity == 8;
-  hipLaunchKernelGGL(ob_local_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(256), 0, s, k, tiles_x, conn8, parent);
-  const long n_h = (long)(tiles_y - 1) * W, n_v = (long)(tiles_x - 1) * H;
-  if (n_h + n_v > 0)
-    hipLaunchKernelGGL(ob_merge_kernel, dim3((unsigned)((n_h + n_v + 255) / 256), (unsigned)B), dim3(256), 0, s, k, n_h,
-                       n_v, conn8, parent);
-  hipLaunchKernelGGL(ob_flatten_kernel, dim3((unsigned)pix_blocks, (unsigned)B), dim3(256), 0, s, parent, hw, labels);
+  ob_roots(k, B, connectivity == 8, parent, labels, s);
+  s2s_number_sets(labels, parent, chunk, B, H, W, min_area, max_objects, count, (long long*)kept_pixels, largest,
+                  (long long*)size_hist, tab_area, tab_bbox, (long long*)tab_sums, s);
+  S2S_LAUNCH_CHECK();
+  return S2S_OK;
+}
+
+extern "C" int s2s_objects_label_seeded(const void* mask, long pitch, long img_stride, int fg_bits, const void* marker,
+                                        long marker_pitch, long marker_img_stride, int seed_bits, int min_seed,
+                                        int invert, int B, int H, int W, int connectivity, int min_area,
+                                        int max_objects, int* scratch, int* labels, int* count, long* kept_pixels,
+                                        int* largest, long* size_hist, int* tab_area, int* tab_bbox, long* tab_sums,
+                                        void* out_mask, long out_pitch, long out_img_stride, int* candidates,
+                                        int* seeded, long* seed_pixels, void* stream) {
+  if (!mask || !marker || !scratch || !labels || !count || !kept_pixels || !largest || !size_hist || !candidates ||
+      !seeded || !seed_pixels)
+    return S2S_ERR_NULL;
+  if (max_objects > 0 && (!tab_area || !tab_bbox || !tab_sums)) return S2S_ERR_NULL;
+  if (!ob_shape_ok(B, H, W) || (connectivity != 4 && connectivity != 8) || min_area < 1 || max_objects < 0 ||
+      fg_bits < 1 || fg_bits > 255 || pitch < W || (B > 1 && img_stride < pitch * (long)H) ||
+      (long)B * max_objects > 0x7fffffffL)
+    return S2S_ERR_SHAPE;
+  if (seed_bits < 1 || seed_bits > 255 || min_seed < 1 || (invert != 0 && invert != 1) || marker_pitch < W ||
+      (B > 1 && marker_img_stride < marker_pitch * (long)H))
+    return S2S_ERR_SHAPE;
+  if (out_mask && (out_pitch < W || (B > 1 && out_img_stride < out_pitch * (long)H))) return S2S_ERR_SHAPE;
+  hipStream_t s = (hipStream_t)stream;
+  const long hw = (long)H * W;
+  if ((long)cdiv(H, OT_H) * cdiv(W, OT_W) > 0x7fffffffL) return S2S_ERR_SHAPE;
+  int* parent = scratch;
+  int* chunk = scratch + (long)B * hw;
+  const ObMask k{(const unsigned char*)mask, pitch, img_stride, fg_bits, H, W};
+  ob_roots(k, B, connectivity == 8, parent, labels, s);
+  ObSeed sd;
+  sd.marker = (const unsigned char*)marker;
+  sd.pitch = marker_pitch;
+  sd.img = marker_img_stride;
+  sd.bits = seed_bits;
+  sd.min_seed = min_seed;
+  sd.invert = invert;
+  sd.mask = k.m;
+  sd.mask_pitch = pitch;
+  sd.mask_img = img_stride;
+  sd.keep_tissue = fg_bits == 1;
+  sd.out = (unsigned char*)out_mask;
+  sd.out_pitch = out_pitch;
+  sd.out_img = out_img_stride;
+  sd.W = W;
+  const dim3 pix((unsigned)((hw + 255) / 256), (unsigned)B);
+  hipLaunchKernelGGL(ob_seed_zero_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, B, candidates, seeded,
+                     (long long*)seed_pixels);
+  hipLaunchKernelGGL(ob_zero_kernel, pix, dim3(256), 0, s, labels, hw, parent);
+  const dim3 pix8((unsigned)((hw + 256L * OB_SEED_PER - 1) / (256L * OB_SEED_PER)), (unsigned)B);
+  hipLaunchKernelGGL(ob_seed_kernel, pix8, dim3(256), 0, s, labels, hw, sd, parent, (long long*)seed_pixels);
+  hipLaunchKernelGGL(ob_gate_kernel, pix8, dim3(256), 0, s, labels, parent, hw, sd, candidates, seeded);
   s2s_number_sets(labels, parent, chunk, B, H, W, min_area, max_objects, count, (long long*)kept_pixels, largest,
                   (long long*)size_hist, tab_area, tab_bbox, (long long*)tab_sums, s);
   S2S_LAUNCH_CHECK();
